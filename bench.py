@@ -4,21 +4,46 @@
 Workload (BASELINE.json configs[3], DESIGN.md "Measurement"): a 262144 x
 262144 torus, B3/S23, Bernoulli(0.5) splitmix64 board (seed 0x5EED),
 row-sharded over N GPUs (strong scaling; N = 1 runs the whole board on one
-GPU).  A "step" is one generation of the whole board.  Every GPU also runs
-the single-GPU roofline case of configs[2] (65536^2) before the timed
-262144^2 window -- the same sequence at every N -- and rank 0 reports it
-under "secondary".
+GPU).  A "step" is one generation of the whole board.  With --full every GPU
+also runs the single-GPU roofline case of configs[2] (65536^2) before the
+timed 262144^2 window -- the same sequence at every N -- and rank 0 reports
+it under "secondary".
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
+
+A plain run does what the headline figure needs and no more: it creates the
+board, settles, warms up, times the K generations, writes its outputs if
+--dump-outputs is given and prints the result line (value, ms_per_step, the
+timed launches' roofline).  --full adds everything else around the same
+headline window: the 65536^2, 4096^2 and default-board runs ("secondary"),
+the window with the fused state hash, the N = 1 ring-schedule windows, the
+N > 1 fault drill, the CPU baselines, and the parity checks of every window
+against the committed golden tables (the --no-* options drop single parts of
+it).  With --full every GPU runs the single-GPU roofline case of configs[2]
+before the timed 262144^2 window.
+
+--dump-outputs DIR writes what the timed window left behind, as float .npy
+files two builds can be compared by: board_sample.npy (the 0/1 cells of a
+fixed, seeded choice of whole rows of the board after the last timed
+generation, first and last row included; board_sample_rank<r>.npy per shard
+at N > 1), board_sample_rows.npy (their row numbers), state_hash.npy (the
+whole board's state hash as [high, low] 32-bit halves) and, with --hash,
+step_hashes.npy (the timed generations' hashes, one [high, low] row each).
+The board and its seed are fixed, so the same arguments give the same files.
 
 value = W*H*K / max-over-ranks wall time of the K timed generations (GCUPS),
 with the board already resident in HBM.  Before its W warm-up steps every
 timed board is seeded, stepped untimed for a short settle (the chip's clock
 recovers over ~20 launches after an idle gap such as the 16 GiB allocation,
 profiles/r02_warmup_curve.txt) and re-seeded, so the timed epochs are W + K
-from the seed and every window's hash is checked against a committed golden
-table (tests/golden/bench_*.json).
+from the seed and, with --full, every window's hash is checked against a
+committed golden table (tests/golden/bench_*.json).  The tables end (epoch
+140 at 262144^2, 1100 at 65536^2): a window that a larger --steps carries
+past the end is listed under parity_unchecked, and the same engine is then
+re-seeded and stepped to the table's last epoch and checked there, so every
+board's kernels are checked at any --steps; only a mismatch, or a board
+without any table, fails the run.
 
 No torch: the process is one rank of the launcher (RANK / WORLD_SIZE /
 LOCAL_RANK from the environment), the RCCL unique id travels through a file
@@ -99,6 +124,13 @@ def parse():
     ap.add_argument("--gpp", type=int, default=DEFAULT_GPP,
                     help="generations fused per HBM pass (temporal blocking depth 1..12; 0 = automatic)")
     ap.add_argument("--hash", action="store_true", help="fuse the per-generation state hash")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed generations, write the board they left (a fixed, seeded sample of its rows "
+                         "as 0/1 cells) and its state hash as float .npy files into DIR")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline window: the secondary boards, the hashed window, "
+                         "the N = 1 ring-schedule windows, the N > 1 fault drill, the CPU baselines and the parity "
+                         "checks against the golden tables (the options below concern these parts only)")
     ap.add_argument("--no-secondary", action="store_true")
     ap.add_argument("--no-ring", action="store_true", help="skip the N = 1 ring-schedule measurements")
     ap.add_argument("--no-cpu", action="store_true")
@@ -111,7 +143,10 @@ def parse():
                          "printed without it, parity_ok false)")
     ap.add_argument("--allow-unchecked", action="store_true",
                     help="exit 0 when a window has no golden value (boards without a table); a mismatch still fails")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return a
 
 
 class Job:
@@ -304,12 +339,39 @@ class Parity:
         g = self.tables[shape]
         return g[epoch] if g is not None and epoch < len(g) else None
 
+    def last_epoch(self, shape):
+        """The last epoch `shape`'s golden table reaches, or None without a table."""
+        self._golden(shape, 0)
+        g = self.tables[shape]
+        return len(g) - 1 if g else None
+
     def board(self, what, shape, epoch, value):
         g = self._golden(shape, epoch)
         c = {"what": what, "board": f"{shape[0]}x{shape[1]}", "epoch": epoch, "hash": f"{value:#018x}",
              "golden": None if g is None else f"{g:#018x}", "match": None if g is None else value == g}
+        if g is None and self.last_epoch(shape) is not None:
+            c["table_ends_at"] = self.last_epoch(shape)
         self.checks.append(c)
         return {k: c[k] for k in ("epoch", "hash", "golden", "match")}
+
+    def within_table(self, what, eng, job, shape, epoch, hashed=False):
+        """The stand-in for a window that ran past its board's golden table
+        (a --steps the tables do not reach): the same engine, re-seeded and
+        stepped to the table's last epoch on the passes it just timed, and
+        its hash (summed over the ranks) checked there.  Nothing when the
+        window ended inside the table or the board has none.  Returns the
+        check, or None."""
+        last = self.last_epoch(shape)
+        if last is None or epoch <= last:
+            return None
+        eng.seed(GOLDEN_SEED)
+        if hashed:
+            hs = eng.step(last, hashes=True)
+            self.sequence(what + " (per-generation hashes)", shape, 1,
+                          eng.allreduce_u64(hs) if job is not None and job.world > 1 else hs)
+        else:
+            eng.step(last)
+        return self.board(what, shape, last, global_hash(eng, job))
 
     def sequence(self, what, shape, first_epoch, values):
         gs = [self._golden(shape, first_epoch + k) for k in range(len(values))]
@@ -319,14 +381,25 @@ class Parity:
              "checked": len(known), "mismatched_epochs": bad[:16],
              "last_hash": f"{int(values[-1]):#018x}" if len(values) else None,
              "match": (not bad) if known else None}
+        if not known and self.last_epoch(shape) is not None:
+            c["table_ends_at"] = self.last_epoch(shape)
         self.checks.append(c)
         return c
 
     def failed(self, allow_unchecked=False):
-        """The checks that did not match (or, unless allow_unchecked, that had
-        no golden value): short labels for the line's closing parity_failed."""
+        """The checks that did not match (or, unless allow_unchecked, whose
+        board has no golden table): short labels for the line's closing
+        parity_failed.  A window that ran past the end of its board's table
+        does not fail the run: it is listed by unchecked(), and the same
+        engine is checked inside the table instead (within_table)."""
         return [f'{c["what"]} [{c["board"]}]: ' + ("mismatch" if c["match"] is False else "no golden value")
-                for c in self.checks if c["match"] is False or (c["match"] is None and not allow_unchecked)]
+                for c in self.checks
+                if c["match"] is False or (c["match"] is None and "table_ends_at" not in c and not allow_unchecked)]
+
+    def unchecked(self):
+        """The windows that ended past their board's golden table."""
+        return [f'{c["what"]} [{c["board"]}]: past the table (epochs 0..{c["table_ends_at"]})'
+                for c in self.checks if c["match"] is None and "table_ends_at" in c]
 
     def report(self):
         ms = [c["match"] for c in self.checks]
@@ -694,6 +767,10 @@ def secondary_run(GolEngine, a, local, parity=None):
         n1 = max(a.steps, 256)
         dt1, kms1, l1, g1, c1, _ = fresh_window(e2, None, n1, 0, a.hash, 50.0, 16)
         p1 = chk("65536^2 single-generation passes: gol_hash after K", shape, n1, e2.hash())
+        if parity is not None:
+            e2.set_tuning(band_rows=a.band, gens_per_pass=a.gpp)
+            parity.within_table("65536^2 board re-run to its table's last epoch: gol_hash", e2, None, shape,
+                                max(n_s + w_s, n2, n1), a.hash)
     sh = f"{S}x{S}"
     r2 = roofline(kms2, l2, g2, S * S, plan2, sh, "N1", a.hash, c2)
     r1 = roofline(kms1, l1, g1, S * S, [1] * n1, sh, "N1", a.hash, c1)
@@ -862,6 +939,8 @@ def ring_schedule_runs(GolEngine, N, a, local, eng, W, H, parity):
         "ms_per_step": round(dt / a.steps * 1e3, 4), "pass_plan": eng.pass_plan(min(a.steps, 1024)),
         "exchange": ring_stats(st, launches),
         "parity": parity.board("whole-board self-ring: gol_hash after W + K", (W, H), a.warmup + a.steps, eng.hash())}
+    parity.within_table("whole-board self-ring re-run to its table's last epoch: gol_hash", eng, None, (W, H),
+                        a.warmup + a.steps)
     rows8 = H // 8
     shape8 = (W, rows8)
     with GolEngine(W, H, topology="torus", rule="life", device=local, row0=0, rows=rows8) as e8:
@@ -887,6 +966,8 @@ def ring_schedule_runs(GolEngine, N, a, local, eng, W, H, parity):
         p8 = parity.board("N = 8 rank's shard, self-ring: gol_hash after W + K", shape8, a.warmup + a.steps,
                           e8.hash())
         plan8 = e8.pass_plan(min(a.steps, 1024))
+        parity.within_table("N = 8 rank's shard, self-ring re-run to its table's last epoch: gol_hash", e8, None,
+                            shape8, a.warmup + a.steps)
     out["per_rank_shard_self_ring"] = {
         "shard": f"{W}x{rows8} (one rank of N = 8)", "value": round(W * rows8 * a.steps / dt8 / 1e9, 2),
         "unit": "GCUPS", "warmup": f"{a.warmup} ({warm}, after 1 s idle)", "ms_per_step": round(dt8 / a.steps * 1e3, 4),
@@ -1056,6 +1137,52 @@ def fault_drill(job, N, GolEngine, eng, a, W, H, local, parity):
     }, eng
 
 
+DUMP_SAMPLE_BYTES = 32 << 20  # float32 cells of the sampled rows, all ranks together
+
+
+def _u64_halves(values):
+    """uint64 values as float64 [high, low] 32-bit halves (exact in float64)."""
+    import numpy as np
+    v = np.asarray(values, dtype=np.uint64).reshape(-1)
+    return np.stack([(v >> np.uint64(32)).astype(np.float64), (v & np.uint64(0xFFFFFFFF)).astype(np.float64)], axis=1)
+
+
+def dump_outputs(dirname, eng, job, step_hashes):
+    """--dump-outputs: what the timed window computed, as float .npy files.
+
+    The window's result is the board after its last generation (what
+    snapshot() hands a caller): its cells in a fixed choice of whole rows of
+    this rank's shard -- the first and the last row, the others drawn by a
+    generator seeded with the board's seed and the rank -- as float32 0/1,
+    their row numbers, the whole board's state hash (summed over the ranks)
+    and, when the window fused them, its per-generation hashes (this rank's
+    partials summed over the ranks).  Every rank calls it (the hashes go
+    through the ring's all-reduce); rank 0 writes the hashes."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    ranks = job.world > 1
+    snap = eng.snapshot()
+    rows, words = snap.shape
+    n = int(max(1, min(rows, DUMP_SAMPLE_BYTES // job.world // (words * 32 * 4))))
+    pick = np.array([0, rows - 1][:n], dtype=np.int64)
+    if n > 2:
+        rng = np.random.default_rng([GOLDEN_SEED, job.rank])
+        pick = np.sort(np.concatenate([pick, 1 + rng.choice(rows - 2, size=n - 2, replace=False)]))
+    cells = np.unpackbits(np.ascontiguousarray(snap[pick]).view(np.uint8), axis=1, bitorder="little")
+    del snap
+    cells = cells[:, :max(1, DUMP_SAMPLE_BYTES // job.world // (4 * n))]  # a row wider than the whole budget
+    tag = f"_rank{job.rank}" if ranks else ""
+    np.save(os.path.join(dirname, f"board_sample{tag}.npy"), cells.astype(np.float32))
+    np.save(os.path.join(dirname, f"board_sample_rows{tag}.npy"), (pick + eng.row0).astype(np.float64))
+    h = global_hash(eng, job)
+    if step_hashes is not None and ranks:
+        step_hashes = eng.allreduce_u64(step_hashes)
+    if job.rank == 0:
+        np.save(os.path.join(dirname, "state_hash.npy"), _u64_halves([h])[0])
+        if step_hashes is not None:
+            np.save(os.path.join(dirname, "step_hashes.npy"), _u64_halves(step_hashes))
+
+
 def main():
     a = parse()
     # one JSON line on stdout: native libraries (RCCL's version banner at
@@ -1073,7 +1200,9 @@ def main():
 
     W = H = a.board
     parity = Parity()
-    # Every GPU runs the same sequence at every N: the 65536^2 measurement
+    # A plain run times the headline window alone; everything else is --full's.
+    want_secondary = a.full and not a.no_secondary
+    # With --full every GPU runs the same sequence at every N: the 65536^2 measurement
     # (BASELINE.json configs[2]) first, then the 262144^2 workload.  At N = 1
     # the 65536^2 board comes first because a board allocated after the
     # 16 GiB one was freed stepped ~5 % slower (scripts/alloc_order.py); at
@@ -1082,7 +1211,7 @@ def main():
     # 65536^2 measurement.  Either way the timed window then starts from its
     # own settle (fresh_window).
     secondary = None
-    if world == 1 and not a.no_secondary:
+    if world == 1 and want_secondary:
         secondary = secondary_run(GolEngine, a, local, parity)
         secondary["configs1_4096"] = small_board_run(GolEngine, local, parity)
         secondary["configs0_default_board"] = default_board_run(GolEngine, local, parity)
@@ -1091,7 +1220,7 @@ def main():
     eng.set_tuning(band_rows=a.band, gens_per_pass=a.gpp)
     if world > 1:
         job.join(eng, N)
-        if not a.no_secondary:
+        if want_secondary:
             secondary = secondary_run(GolEngine, a, local, parity if rank == 0 else None)
             secondary["note"] = f"measured on rank {rank}'s GPU; each of the {world} ranks ran it on its own GPU"
 
@@ -1100,17 +1229,20 @@ def main():
     e1 = a.warmup + a.steps
     rank_times = list(getattr(timed_run, "rank_times", []))
     ranks_diag = rank_table(job, N, stats, dt if world == 1 else rank_times[rank], info) if world > 1 else None
-    if hs is not None:
-        parity.sequence("fused per-generation hashes of the W + K generations (global: shard partials "
-                        "summed by gol_comm_allreduce_u64 at N > 1)",
-                        (W, H), 1, eng.allreduce_u64(hs) if world > 1 else hs)
-    parity.board("gol_hash of the board after the W + K generations (summed over the ranks)", (W, H), e1,
-                 global_hash(eng, job))
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, eng, job, None if hs is None else hs[-a.steps:])
+    if a.full:
+        if hs is not None:
+            parity.sequence("fused per-generation hashes of the W + K generations (global: shard partials "
+                            "summed by gol_comm_allreduce_u64 at N > 1)",
+                            (W, H), 1, eng.allreduce_u64(hs) if world > 1 else hs)
+        parity.board("gol_hash of the board after the W + K generations (summed over the ranks)", (W, H), e1,
+                     global_hash(eng, job))
     eng_info = {g: eng.occupancy(g) for g in range(1, 13)}
     plan = eng.pass_plan(min(a.steps, 1024), hashes=a.hash)
     value = W * H * a.steps / dt / 1e9
     hashed = None
-    if not a.hash:
+    if a.full and not a.hash:
         # the same workload with the fused per-generation state hash (the
         # parity contract's output: one u64 per generation),
         # continuing from the board the timed run left; at N > 1 the shards'
@@ -1126,6 +1258,12 @@ def main():
                   "frac_of_unhashed": round(vh / value, 4), "pass_plan": hplan,
                   "roofline": roofline(kmsh, lh, gh, W * rows if world == 1 else W * max(rows - round(2 * gh / max(lh, 1)), 0),
                                        hplan, f"{W}x{rows}", "N1" if world == 1 else "ring", True, ch)}
+    if a.full:
+        # a --steps past the golden table: the same shards checked inside it
+        ran_to = e1 if a.hash else 2 * e1
+        for h in ([True] if a.hash else [False, True]):
+            parity.within_table(f"headline board re-run to its table's last epoch{' (fused hash)' if h else ''}: "
+                                "gol_hash summed over the ranks", eng, job, (W, H), ran_to, h)
     # dominant kernel: the whole-shard (N=1) or interior-rows (N>1) launch of a
     # pass; G = generations that launch advances (the library's choice when --gpp 0)
     G = gcov / launches if launches else (a.gpp or 1)  # mean depth of the timed passes
@@ -1137,7 +1275,7 @@ def main():
     if roof is not None:
         roof["kernel"] = kernel_label(eng_info, plan, ilv)
     ring = None
-    if world == 1 and not a.no_ring and not a.hash:
+    if a.full and world == 1 and not a.no_ring and not a.hash:
         ring = ring_schedule_runs(GolEngine, N, a, local, eng, W, H, parity)
     absorbed, absorbed_last = N.absorbed()
     runtime = dict(info, rccl_statuses_absorbed=absorbed)
@@ -1171,6 +1309,8 @@ def main():
         "parity": parity.report(),
         "runtime": runtime,
     }
+    if not a.full:
+        del out["parity"]  # nothing was checked: the golden tables are --full's
     if world > 1:
         rt = rank_times
         d = ranks_diag
@@ -1200,7 +1340,7 @@ def main():
     job.barrier()
     if rank == 0 and secondary is not None:
         out["secondary"] = secondary
-    if world > 1 and not a.no_fault:
+    if a.full and world > 1 and not a.no_fault:
         # The drill runs after the measured windows, on a ring rebuilt around a
         # lost rank -- a path that has not met every multi-GPU fabric yet.  A
         # watchdog keeps it from costing the line: past --fault-timeout every
@@ -1240,14 +1380,19 @@ def main():
             out["fault_recovery"] = fault
     if eng is not None:
         eng.close()
-    if rank == 0 and world == 1 and not a.no_cpu:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu:
         out["cpu_baseline"] = cpu_baseline(W, a.cpu_seconds)
-    # The compact parity verdict closes the line, so a tail of it always shows
-    # the headline's own check; a failed (or, without --allow-unchecked,
-    # unchecked) window fails the run after the line is printed.
-    failed = parity.failed(a.allow_unchecked)
-    out["parity_failed"] = failed
-    out["parity_ok"] = not failed
+    # With --full the compact parity verdict closes the line, so a tail of it
+    # always shows the headline's own check; a mismatch (or, without
+    # --allow-unchecked, a board without a golden table) fails the run after
+    # the line is printed; windows past the end of their table are named in
+    # parity_unchecked.  A plain run checks nothing and says nothing about parity.
+    failed = parity.failed(a.allow_unchecked) if a.full else []
+    if a.full:
+        if parity.unchecked():
+            out["parity_unchecked"] = parity.unchecked()
+        out["parity_failed"] = failed
+        out["parity_ok"] = not failed
     if rank == 0:
         sys.stdout.flush()
         os.write(result_fd, (json.dumps(out) + "\n").encode())

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Reconcile the two clock readings of the bench's timed launches (VERDICT
 r02 item 4): one `rocprofv3 --pmc GRBM_GUI_ACTIVE SQ_INSTS_VALU` pass over the
-driver's exact command (`bench.py --steps 20 --warmup 5`), whose output line
+driver's command (`bench.py --full --steps 20 --warmup 5`), whose output line
 carries the in-kernel probe clock of the same launches (held_clock.ghz).
 
 For the headline window's timed launches -- the last len(plan) step-kernel
@@ -58,7 +58,7 @@ def main():
     with open(os.path.join(src, "bench_under_pmc.json")) as f:
         b = json.loads([ln for ln in f if ln.startswith("{")][-1])
     W, H = b["config"]["board"]
-    lines = [f"rocprofv3 --pmc GRBM_GUI_ACTIVE SQ_INSTS_VALU -- python3 bench.py --steps {b['steps']} "
+    lines = [f"rocprofv3 --pmc GRBM_GUI_ACTIVE SQ_INSTS_VALU -- python3 bench.py --full --steps {b['steps']} "
              f"--warmup {b['warmup']}  (one run: counters and the bench line of the same launches)", ""]
     for k, (label, rec) in enumerate((("headline window", b), ("hashed window", b.get("with_state_hash")))):
         ro = rec["roofline"]

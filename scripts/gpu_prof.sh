@@ -6,10 +6,10 @@ cd $GRAFT_REPO_ROOT
 export TMPDIR=/tmp
 P=gpurun_out/prof
 mkdir -p $P
-timeout -k 10 600 rocprofv3 --kernel-trace --stats -T -d $P/bench_trace -o bench --output-format csv -- python3 bench.py --steps 60 --warmup 6 --cpu-seconds 10 > $P/bench_under_rocprof.json 2> $P/bench_under_rocprof.err
+timeout -k 10 600 rocprofv3 --kernel-trace --stats -T -d $P/bench_trace -o bench --output-format csv -- python3 bench.py --full --steps 60 --warmup 6 --cpu-seconds 10 > $P/bench_under_rocprof.json 2> $P/bench_under_rocprof.err
 rc=$?; echo "rocprof bench rc=$rc"; tail -2 $P/bench_under_rocprof.json
 [ $rc -eq 0 ] || exit $rc
-timeout -k 10 600 python3 bench.py --steps 60 --warmup 6 --cpu-seconds 10 > $P/bench.json 2> $P/bench.err
+timeout -k 10 600 python3 bench.py --full --steps 60 --warmup 6 --cpu-seconds 10 > $P/bench.json 2> $P/bench.err
 rc=$?; echo "bench rc=$rc"; cat $P/bench.json
 [ $rc -eq 0 ] || exit $rc
 for edge in 262144 65536; do

@@ -59,7 +59,7 @@ def main():
         dur = (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e6
         groups[(r["Kernel_Name"], int(r["Grid_Size_X"]), int(r["Grid_Size_Y"]))].append(dur)
     b = benches["bench_under_rocprof.json"]
-    lines = [f"rocprofv3 --kernel-trace --stats -- python3 bench.py --steps {b['steps']} --warmup {b['warmup']}",
+    lines = [f"rocprofv3 --kernel-trace --stats -- python3 bench.py --full --steps {b['steps']} --warmup {b['warmup']}",
              "per (kernel, grid): dispatches, mean / median / min ms", ""]
     for (name, gx, gy), d in sorted(groups.items(), key=lambda kv: -sum(kv[1])):
         lines.append(f"{name:40s} grid=({gx},{gy}) n={len(d):3d} mean={statistics.mean(d):.4f} "

@@ -43,7 +43,7 @@ def _run(world, tmp_path, *args, extra_env=None, rc=0):
 
 @pytest.mark.parametrize("world", [2, 3])
 def test_multirank_bench_line(tmp_path, world):
-    outs, logs = _run(world, tmp_path, "--steps", "20", "--warmup", "5", "--no-cpu", "--no-fault")
+    outs, logs = _run(world, tmp_path, "--full", "--steps", "20", "--warmup", "5", "--no-cpu", "--no-fault")
     lines = [ln for ln in outs[0].splitlines() if ln.strip()]
     assert len(lines) == 1, outs[0]
     assert all(not o.strip() for o in outs[1:])  # only rank 0 prints
@@ -119,7 +119,7 @@ def test_multirank_bench_flags_a_wrong_shard(tmp_path):
     would do) turns parity.match false, the mismatching epochs are named, the
     line closes with parity_ok false, and every rank exits non-zero after the
     line is printed."""
-    outs, _ = _run(2, tmp_path, "--steps", "20", "--warmup", "5", "--no-cpu", "--no-secondary", "--no-fault",
+    outs, _ = _run(2, tmp_path, "--full", "--steps", "20", "--warmup", "5", "--no-cpu", "--no-secondary", "--no-fault",
                    extra_env={"FAKE_CORRUPT_RANK": "1"}, rc=3)
     d = json.loads([ln for ln in outs[0].splitlines() if ln.strip()][0])
     par = d["parity"]
@@ -134,7 +134,7 @@ def test_single_rank_keeps_cpu_baseline_slot(tmp_path):
     """N = 1 through the same runner: the 65536^2 run comes before the whole
     board (allocation order) and no communicator is created for the headline
     run (the self-ring runs come after it)."""
-    outs, logs = _run(1, tmp_path, "--steps", "12", "--warmup", "2", "--no-cpu", "--no-ring")
+    outs, logs = _run(1, tmp_path, "--full", "--steps", "12", "--warmup", "2", "--no-cpu", "--no-ring")
     d = json.loads([ln for ln in outs[0].splitlines() if ln.strip()][0])
     assert d["n_gpus"] == 1 and d["value"] > 0 and "note" not in d["secondary"]
     c1 = d["secondary"]["configs1_4096"]  # BASELINE.json configs[1], checked against golden.json
@@ -159,7 +159,7 @@ def test_single_rank_ring_windows_carry_parity(tmp_path):
     shard's windows (driver's sequence and settled) end at epoch W + K from
     the seed and are checked against bench_262144.json and
     bench_262144x32768.json; a wrong shard hash would show on its sub-line."""
-    outs, logs = _run(1, tmp_path, "--steps", "20", "--warmup", "5", "--no-cpu")
+    outs, logs = _run(1, tmp_path, "--full", "--steps", "20", "--warmup", "5", "--no-cpu")
     d = json.loads([ln for ln in outs[0].splitlines() if ln.strip()][0])
     ring = d["ring_schedule_n1"]
     for k in ("whole_board_self_ring", "per_rank_shard_driver_window", "per_rank_shard_self_ring"):
@@ -180,7 +180,7 @@ def test_torchrun_launch_like_the_driver(tmp_path):
     env = dict(os.environ, FAKE_LOG_DIR=str(tmp_path), OMP_NUM_THREADS="1")
     p = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                         "--master-addr", "127.0.0.1", "--master-port", str(port), RUNNER,
-                        "--gpus", "2", "--steps", "20", "--warmup", "5", "--no-cpu", "--no-fault"],
+                        "--gpus", "2", "--full", "--steps", "20", "--warmup", "5", "--no-cpu", "--no-fault"],
                        env=env, capture_output=True, text=True, timeout=180)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
@@ -203,7 +203,7 @@ def test_fault_drill_sub_line(tmp_path, world):
     epoch -- and the N - 1 survivors join a new ring and step on to 50.
     Every global hash (before, replayed, at the loss, after, final) equals
     bench_262144.json, and the sub-line carries its parity and wall times."""
-    outs, logs = _run(world, tmp_path, "--steps", "20", "--warmup", "5", "--no-cpu", "--no-secondary")
+    outs, logs = _run(world, tmp_path, "--full", "--steps", "20", "--warmup", "5", "--no-cpu", "--no-secondary")
     d = json.loads([ln for ln in outs[0].splitlines() if ln.strip()][0])
     assert all(not o.strip() for o in outs[1:])
     f = d["fault_recovery"]
@@ -245,7 +245,7 @@ def test_fault_drill_watchdog(tmp_path):
     """A ring rebuild that never completes must not cost the measured line:
     past --fault-timeout every rank stops (exit 4), rank 0 having printed the
     line with fault_recovery marked timed out and parity_ok false."""
-    outs, _ = _run(3, tmp_path, "--steps", "20", "--warmup", "5", "--no-cpu", "--no-secondary",
+    outs, _ = _run(3, tmp_path, "--full", "--steps", "20", "--warmup", "5", "--no-cpu", "--no-secondary",
                    "--fault-timeout", "8", extra_env={"FAKE_HANG_REJOIN": "1"}, rc=None)
     d = json.loads([ln for ln in outs[0].splitlines() if ln.strip()][0])
     assert d["value"] > 0 and d["parity"]["match"] is True  # the measured windows are intact
@@ -261,7 +261,7 @@ def test_fault_drill_skips_without_room(tmp_path):
     """No directory with room for the checkpoint files: every rank skips the
     drill together (rank 0 decides), the line says so, and the measured
     windows stand (exit 0)."""
-    outs, logs = _run(2, tmp_path, "--steps", "20", "--warmup", "5", "--no-cpu", "--no-secondary",
+    outs, logs = _run(2, tmp_path, "--full", "--steps", "20", "--warmup", "5", "--no-cpu", "--no-secondary",
                       extra_env={"FAKE_NO_ROOM": "1"})
     d = json.loads([ln for ln in outs[0].splitlines() if ln.strip()][0])
     assert d["fault_recovery"]["status"] == "skipped" and d["parity_ok"] is True
@@ -272,7 +272,7 @@ def test_fault_drill_error_on_rank0(tmp_path):
     """A drill that fails on rank 0 (a checkpoint write raising) still gets
     the measured line out: status error, parity_ok false, exit 3 on rank 0;
     the peers, left waiting in a collective, stop at the watchdog (exit 4)."""
-    outs, _ = _run(3, tmp_path, "--steps", "20", "--warmup", "5", "--no-cpu", "--no-secondary",
+    outs, _ = _run(3, tmp_path, "--full", "--steps", "20", "--warmup", "5", "--no-cpu", "--no-secondary",
                    "--fault-timeout", "8", extra_env={"FAKE_DRILL_RAISE": "0"}, rc=None)
     d = json.loads([ln for ln in outs[0].splitlines() if ln.strip()][0])
     assert d["fault_recovery"]["status"] == "error" and "No space left" in d["fault_recovery"]["error"]
@@ -286,10 +286,113 @@ def test_fault_drill_error_on_a_peer(tmp_path):
     the peer exits (and a third rank's collective may break with it, so it
     can be named too).  Either way rank 0's line names the peer's exception
     under fault_recovery.rank_errors and fails parity."""
-    outs, _ = _run(3, tmp_path, "--steps", "20", "--warmup", "5", "--no-cpu", "--no-secondary",
+    outs, _ = _run(3, tmp_path, "--full", "--steps", "20", "--warmup", "5", "--no-cpu", "--no-secondary",
                    "--fault-timeout", "8", extra_env={"FAKE_DRILL_RAISE": "1"}, rc=None)
     d = json.loads([ln for ln in outs[0].splitlines() if ln.strip()][0])
     fr = d["fault_recovery"]
     assert fr["status"] in ("timed out", "error") and "1" in fr["rank_errors"] and "0" not in fr["rank_errors"]
     assert "No space left" in fr["rank_errors"]["1"]
     assert d["parity_ok"] is False
+
+
+HEADLINE_KEYS = ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step")
+
+
+def test_plain_run_times_the_headline_window_only(tmp_path):
+    """Without --full the N = 1 run creates the 262144^2 board alone, settles,
+    re-seeds, runs the W warm-up and exactly K timed generations and prints
+    the line: no other board, no hashed window, no ring, no hash read-back,
+    no CPU baseline and no parity fields -- at a W + K the golden table does
+    not reach it still exits 0."""
+    outs, logs = _run(1, tmp_path, "--steps", "200", "--warmup", "7")
+    d = json.loads([ln for ln in outs[0].splitlines() if ln.strip()][0])
+    assert all(k in d for k in HEADLINE_KEYS) and d["steps"] == 200 and d["warmup"] == 7
+    assert d["value"] > 0 and d["ms_per_step"] > 0 and d["unit"] == "GCUPS" and d["higher_is_better"] is True
+    assert d["roofline"]["bound"] == "valu"
+    for k in ("secondary", "with_state_hash", "ring_schedule_n1", "cpu_baseline", "parity", "parity_ok",
+              "parity_failed", "fault_recovery"):
+        assert k not in d, k
+    log = logs[0]
+    assert [ln.split()[1] for ln in log if ln.startswith("create")] == ["262144x262144"]
+    assert not any(ln.split()[0] in ("hash", "comm_init", "allreduce") for ln in log)
+    last_seed = max(i for i, ln in enumerate(log) if ln.startswith("seed"))
+    assert [ln.split()[2:] for ln in log[last_seed + 1:] if ln.startswith("step")] == [["7"], ["200"]]
+
+
+def test_plain_multirank_run_has_no_extras(tmp_path):
+    """Without --full at N = 2: the shards, their ring and the timed window
+    with its per-rank diagnostics; no 65536^2 run, no hashed window, no fault
+    drill."""
+    outs, logs = _run(2, tmp_path, "--steps", "20", "--warmup", "5")
+    d = json.loads([ln for ln in outs[0].splitlines() if ln.strip()][0])
+    assert all(k in d for k in HEADLINE_KEYS) and d["n_gpus"] == 2 and len(d["ranks"]["ms_per_step"]) == 2
+    for k in ("secondary", "with_state_hash", "fault_recovery", "parity", "parity_ok"):
+        assert k not in d, k
+    for log in logs:
+        assert [ln.split()[1] for ln in log if ln.startswith("create")] == ["262144x131072"]
+        last_seed = max(i for i, ln in enumerate(log) if ln.startswith("seed"))
+        assert [ln.split()[2:] for ln in log[last_seed + 1:] if ln.startswith("step")] == [["5"], ["20"]]
+        assert not any(ln.split()[0] in ("hash", "checkpoint", "comm_abort") for ln in log)
+
+
+@pytest.mark.parametrize("world", [1, 2])
+def test_dump_outputs_files(tmp_path, monkeypatch, world):
+    """--dump-outputs: the board the timed window left (epoch W + K), as 0/1
+    float32 cells of a fixed choice of whole rows of every shard (first and
+    last row included), and the whole board's state hash -- the golden value
+    of that epoch -- as float64 halves; the same arguments give the same
+    files again."""
+    import numpy as np
+    got = []
+    for k in range(2):
+        logdir, out = tmp_path / f"log{k}", tmp_path / f"out{k}"
+        logdir.mkdir()
+        _run(world, logdir, "--steps", "20", "--warmup", "5", "--dump-outputs", str(out))
+        got.append({p.name: np.load(p) for p in sorted(out.iterdir())})
+    a, b = got
+    tags = [""] if world == 1 else [f"_rank{r}" for r in range(world)]
+    assert sorted(a) == sorted(["state_hash.npy"] + [f"board_sample{t}.npy" for t in tags] +
+                               [f"board_sample_rows{t}.npy" for t in tags])
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values())
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    assert all(np.array_equal(a[k], b[k]) for k in a)
+    with open(os.path.join(ROOT, "tests", "golden", "bench_262144.json")) as f:
+        want = int(json.load(f)["hashes"][25], 16)
+    hi, lo = a["state_hash.npy"]
+    assert (int(hi) << 32) + int(lo) == want
+    monkeypatch.syspath_prepend(os.path.join(ROOT, "tests"))
+    monkeypatch.setenv("FAKE_LOG_DIR", str(tmp_path))  # the runner module wants one at import
+    from bench_fake_runner import FakeBoard
+    board = FakeBoard(262144, 262144)
+    rows_per = 262144 // world
+    for r, t in enumerate(tags):
+        rows, cells = a[f"board_sample_rows{t}.npy"].astype(np.int64), a[f"board_sample{t}.npy"]
+        assert rows[0] == r * rows_per and rows[-1] == (r + 1) * rows_per - 1 and len(set(rows.tolist())) == len(rows)
+        assert cells.shape == (len(rows), 64) and set(np.unique(cells).tolist()) <= {0.0, 1.0}
+        words = FakeBoard.words(board.rows(rows, 25))
+        want_cells = np.unpackbits(np.ascontiguousarray(words).view(np.uint8), axis=1, bitorder="little")
+        assert np.array_equal(cells, want_cells.astype(np.float32))
+
+
+def test_full_run_past_the_golden_tables(tmp_path):
+    """--full with a --steps the 262144-wide tables (epochs 0..140) do not
+    reach: the windows that end past them are named in parity_unchecked, each
+    such engine is re-seeded, stepped to its table's last epoch and checked
+    there (the headline board unhashed and with the fused hashes), and the
+    run exits 0; the 65536^2 windows still end inside their table."""
+    outs, logs = _run(1, tmp_path, "--full", "--steps", "200", "--warmup", "10", "--no-cpu")
+    d = json.loads([ln for ln in outs[0].splitlines() if ln.strip()][0])
+    assert d["steps"] == 200 and d["parity_ok"] is True and d["parity_failed"] == []
+    assert list(d)[-3:] == ["parity_unchecked", "parity_failed", "parity_ok"]
+    assert len(d["parity_unchecked"]) == 6 and all("past the table (epochs 0..140)" in u for u in d["parity_unchecked"])
+    checks = d["parity"]["checks"]
+    assert all(c["match"] is True for c in checks if c["board"] == "65536x65536")
+    rerun = [c for c in checks if "table's last epoch" in c["what"]]
+    assert [(c["board"], c.get("epoch"), c.get("epochs"), c["match"]) for c in rerun] == [
+        ("262144x262144", 140, None, True), ("262144x262144", None, [1, 140], True),
+        ("262144x262144", 140, None, True), ("262144x262144", 140, None, True), ("262144x32768", 140, None, True)]
+    assert rerun[1]["checked"] == 140
+    assert d["parity"]["match"] is None  # some windows had no golden value
+    log = logs[0]
+    assert [ln.split()[2:] for ln in log if ln.startswith("step 262144x262144 140")] == [["140"], ["140", "hashes"],
+                                                                                         ["140"]]
