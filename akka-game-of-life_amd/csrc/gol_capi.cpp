@@ -2,7 +2,8 @@
 // lifetime, seeding and loading, stepping (gol_step: the pass plan of
 // gol_schedule.cpp run by gol_ring.cpp's one_pass), state hashes, tuning and
 // the small host-side entry points.  The other entry points live in
-// gol_ring.cpp, gol_group.cpp, gol_checkpoint.cpp and gol_profile.cpp; the
+// gol_ring.cpp, gol_group.cpp, gol_checkpoint.cpp, gol_profile.cpp and
+// gol_region.cpp; the
 // unit map and the reference correspondence are in gol_ctx.h.
 #include <dlfcn.h>
 
@@ -143,9 +144,11 @@ void destroy_impl(gol_ctx* c) {
     for (hipEvent_t ev : {c->ev_ready, c->ev_halo, c->ev_edge, c->ev_snap_ready, c->ev_snap_done})
         if (ev) hip_note(hipEventDestroy(ev), "destroy: hipEventDestroy");
     for (void* p : {(void*)c->snap, (void*)c->clk_buf, (void*)c->plane[0], (void*)c->plane[1], (void*)c->halo_top,
-                    (void*)c->halo_bot, (void*)c->zero_row, (void*)c->slots})
+                    (void*)c->halo_bot, (void*)c->zero_row, (void*)c->slots, (void*)c->region_stage,
+                    (void*)c->census_slots})
         if (p) hip_note(hipFree(p), "destroy: hipFree");
     if (c->host_folded) hip_note(hipHostFree(c->host_folded), "destroy: hipHostFree");
+    if (c->census_host) hip_note(hipHostFree(c->census_host), "destroy: hipHostFree");
     for (hipStream_t st : {c->compute, c->comm, c->edge, c->xfer})
         if (st) hip_note(hipStreamDestroy(st), "destroy: hipStreamDestroy");
     delete c;

@@ -10,6 +10,8 @@
 //   gol_group.cpp      in-process shard groups (gol_group_*)
 //   gol_checkpoint.cpp snapshots, checkpoints, restore and light-cone replay
 //   gol_profile.cpp    kernel timing, the in-kernel clock probe, gol_profile_*
+//   gol_region.cpp     census and windowed pattern I/O (gol_census,
+//                      gol_read_region, gol_write_region)
 //
 // Reference correspondence (src/main/scala/gameoflife/ of the reference):
 //   gol_create   <- BoardCreator.createAllInitialActors (BoardCreator.scala:79-89)
@@ -95,6 +97,15 @@ struct gol_ctx {
     hipEvent_t ev_snap_ready = nullptr, ev_snap_done = nullptr;
     bool snap_pending = false;
     uint64_t snap_epoch = 0;
+    // census and windows (gol_region.cpp), allocated on first use: the staged
+    // window rows this shard owns (packed, ceil(w / 32) words per row), the
+    // census accumulators and the mapped page-locked words their fold lands in
+    uint32_t* region_stage = nullptr;
+    size_t region_stage_words = 0;
+    unsigned long long* census_slots = nullptr;     // kCensusSlots * kCensusSlotStride
+    bool census_clean = false;                      // the slots hold the identity (left so by the fold)
+    unsigned long long* census_host = nullptr;      // kCensusValues, page-locked, mapped
+    unsigned long long* census_host_dev = nullptr;  // ... its device address
     // RCCL
     ncclComm_t nccl = nullptr;
     int rank = 0, nranks = 1;

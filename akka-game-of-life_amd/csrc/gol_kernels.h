@@ -1,6 +1,7 @@
 // gol_kernels.h -- internal interface between the C-ABI host layer
 // (gol_capi.cpp and the units gol_ctx.h lists) and the gfx950 kernels
-// (gol_stencil.h, gol_step_g<G>.hip, gol_misc.hip).  Not installed.
+// (gol_stencil.h, gol_step_g<G>.hip, gol_misc.hip, gol_region.hip).  Not
+// installed.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -162,5 +163,36 @@ hipError_t launch_fold(unsigned long long* slots, uint32_t gens, unsigned long l
 
 // DPP / lane-shift self test: out[64*4] (see gol_selftest in gol_capi.cpp).
 hipError_t launch_selftest(const uint32_t* in, uint32_t* out, hipStream_t stream);
+
+// ---- census and windows (gol_region.hip) -------------------------------------
+
+// Census accumulators: kCensusSlots slots one 64-byte line apart, each
+// {population, min_x, max_x, min_y, max_y} as 64-bit values (the box signed,
+// global coordinates); the identity is {0, INT64_MAX, -1, INT64_MAX, -1}.
+constexpr int kCensusSlots = 64;
+constexpr int kCensusSlotStride = 8;  // u64 per slot
+constexpr int kCensusValues = 5;
+
+// Every slot to the identity.
+hipError_t launch_census_reset(unsigned long long* slots, hipStream_t stream);
+// Population and bounding box of `rows` device rows (16-byte loads: `plane`
+// 16-byte aligned, `pitch` a multiple of 4 words) into the slots.
+hipError_t launch_census(const uint32_t* plane, int64_t pitch, int32_t wwords, int64_t grow0, int32_t rows, int ilv,
+                         unsigned long long* slots, hipStream_t stream);
+// out[0..5) = the slots combined (sum, min, max), which are left at the
+// identity; `out` may be mapped host memory.
+hipError_t launch_census_fold(unsigned long long* slots, unsigned long long* out, hipStream_t stream);
+
+// Window columns [x0, x0 + w) (modulo the row: 32 * wwords columns) of
+// `nrows` device rows starting at `src`, as packed row-major rows of
+// ceil(w / 32) words in `stage`; bits past w are zero.
+hipError_t launch_region_gather(const uint32_t* src, int64_t pitch, int32_t wwords, int ilv, int32_t nrows, int64_t x0,
+                                int64_t w, uint32_t* stage, hipStream_t stream);
+// The reverse: `stage` (as above; bits past w ignored) combined into columns
+// [x0, x0 + w) of `nrows` device rows starting at `dst` under `mode`
+// (GOL_REGION_*), modulo `width` if wrap_x; every other bit is left as it is.
+hipError_t launch_region_scatter(uint32_t* dst, int64_t pitch, int32_t wwords, int64_t width, int ilv, int32_t nrows,
+                                 int64_t x0, int64_t w, const uint32_t* stage, int mode, bool wrap_x,
+                                 hipStream_t stream);
 
 }  // namespace gol

@@ -1,0 +1,175 @@
+// gol_region.cpp -- the board from the user's side without moving a plane:
+// gol_census (population and bounding box, one pass on the device),
+// gol_read_region and gol_write_region (a window of the torus or of the
+// clipped board, gathered from / scattered into the device layout).  They
+// stand for what the reference offered at 7 x 7: the per-cell initialState of
+// BoardCreator.scala:65-70, the CellStateMsg stream a LoggerActor prints
+// (CellActor.scala:89, LoggerActor.scala:30-46) and the counting a reader of
+// that log does by eye.
+#include <algorithm>
+#include <cstring>
+
+#include "gol_ctx.h"
+
+using namespace golc;
+
+namespace {
+
+// A contiguous run of window rows this shard owns: window rows
+// [win_row, win_row + count) are the shard's local rows from local_row on.
+struct RowRun {
+    int64_t win_row, count, local_row;
+};
+
+// The window rows y0 .. y0 + h - 1 (modulo the height) that fall into the
+// shard: at most two runs, one on each side of the y seam.
+int owned_runs(const gol_ctx* ctx, int64_t y0, int64_t h, RowRun runs[2]) {
+    int n = 0;
+    const int64_t first = std::min(h, ctx->height - y0);  // window rows before the seam
+    const int64_t seg[2][3] = {{0, first, y0}, {first, h, y0 - ctx->height}};  // [lo, hi) and board row - window row
+    for (const auto& s : seg) {
+        const int64_t lo = std::max(s[0], ctx->row0 - s[2]);
+        const int64_t hi = std::min(s[1], ctx->row0 + ctx->rows - s[2]);
+        if (lo < hi) runs[n++] = {lo, hi - lo, lo + s[2] - ctx->row0};
+    }
+    return n;
+}
+
+int check_window(gol_ctx* ctx, const char* what, int64_t x0, int64_t y0, int64_t w, int64_t h, const void* buf,
+                 int64_t host_pitch_words) {
+    if (!ctx) return set_err(nullptr, GOL_EINVAL, "%s: null context", what);
+    if (!buf) return set_err(ctx, GOL_EINVAL, "%s: null window buffer", what);
+    if (w < 1 || w > ctx->width || h < 1 || h > ctx->height || x0 < 0 || x0 >= ctx->width || y0 < 0 ||
+        y0 >= ctx->height)
+        return set_err(ctx, GOL_EINVAL, "%s: window %lld x %lld at (%lld, %lld) does not fit a %lld x %lld board", what,
+                       (long long)w, (long long)h, (long long)x0, (long long)y0, (long long)ctx->width,
+                       (long long)ctx->height);
+    if (ctx->topology == GOL_REF_CLIPPED && (x0 + w > ctx->width || y0 + h > ctx->height))
+        return set_err(ctx, GOL_EINVAL, "%s: window %lld x %lld at (%lld, %lld) leaves the clipped %lld x %lld board",
+                       what, (long long)w, (long long)h, (long long)x0, (long long)y0, (long long)ctx->width,
+                       (long long)ctx->height);
+    if (host_pitch_words < (w + 31) / 32)
+        return set_err(ctx, GOL_EINVAL, "%s: host pitch %lld < %lld words per window row", what,
+                       (long long)host_pitch_words, (long long)((w + 31) / 32));
+    return GOL_OK;
+}
+
+// The staging buffer holds `words` words.  Nothing is in flight on it between
+// calls: both region calls synchronise before they return.
+int ensure_stage(gol_ctx* ctx, size_t words) {
+    if (words <= ctx->region_stage_words) return GOL_OK;
+    uint32_t* old = ctx->region_stage;
+    ctx->region_stage = nullptr;  // forgotten before it is freed: a failure leaves nothing to free twice
+    ctx->region_stage_words = 0;
+    if (old) HIP_CHECK(ctx, hipFree(old));
+    if (hipMalloc(&ctx->region_stage, words * sizeof(uint32_t)) != hipSuccess) {
+        (void)hipGetLastError();
+        ctx->region_stage = nullptr;
+        return set_err(ctx, GOL_ENOMEM, "hipMalloc of %zu bytes for the window staging buffer failed",
+                       words * sizeof(uint32_t));
+    }
+    ctx->region_stage_words = words;
+    return GOL_OK;
+}
+
+int ensure_census(gol_ctx* ctx) {
+    if (!ctx->census_slots) {
+        ctx->census_clean = false;
+        HIP_CHECK(ctx, hipMalloc(&ctx->census_slots,
+                                 (size_t)gol::kCensusSlots * gol::kCensusSlotStride * sizeof(unsigned long long)));
+    }
+    if (!ctx->census_host) {
+        // coherent: the fold's stores reach host memory without a cache flush
+        HIP_CHECK(ctx, hipHostMalloc((void**)&ctx->census_host, gol::kCensusValues * sizeof(unsigned long long),
+                                     hipHostMallocMapped | hipHostMallocCoherent));
+        ctx->census_host_dev = nullptr;
+    }
+    if (!ctx->census_host_dev)
+        HIP_CHECK(ctx, hipHostGetDevicePointer((void**)&ctx->census_host_dev, ctx->census_host, 0));
+    return GOL_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int gol_census(gol_ctx* ctx, gol_census_result* out) {
+    if (!ctx || !out) return set_err(ctx, GOL_EINVAL, "gol_census: null argument");
+    if (int rc = bind(ctx)) return rc;
+    if (int rc = ensure_census(ctx)) return rc;
+    if (!ctx->census_clean) HIP_CHECK(ctx, gol::launch_census_reset(ctx->census_slots, ctx->compute));
+    ctx->census_clean = false;  // in use until the fold has left the identity behind
+    HIP_CHECK(ctx, gol::launch_census(ctx->plane[ctx->cur], ctx->pitch, ctx->wwords, ctx->row0, (int32_t)ctx->rows,
+                                      ctx->ilv, ctx->census_slots, ctx->compute));
+    HIP_CHECK(ctx, gol::launch_census_fold(ctx->census_slots, ctx->census_host_dev, ctx->compute));
+    HIP_CHECK(ctx, hipStreamSynchronize(ctx->compute));
+    ctx->census_clean = true;
+    const unsigned long long* v = ctx->census_host;
+    out->population = v[0];
+    out->min_x = (int64_t)v[1];
+    out->max_x = (int64_t)v[2];
+    out->min_y = (int64_t)v[3];
+    out->max_y = (int64_t)v[4];
+    return GOL_OK;
+}
+
+int gol_read_region(gol_ctx* ctx, int64_t x0, int64_t y0, int64_t w, int64_t h, uint32_t* packed_out,
+                    int64_t host_pitch_words) {
+    if (int rc = check_window(ctx, "gol_read_region", x0, y0, w, h, packed_out, host_pitch_words)) return rc;
+    RowRun runs[2];
+    const int nruns = owned_runs(ctx, y0, h, runs);
+    if (nruns == 0) return GOL_OK;  // the window misses this shard
+    if (int rc = bind(ctx)) return rc;
+    const int64_t sw = (w + 31) / 32;
+    int64_t owned = 0;
+    for (int k = 0; k < nruns; ++k) owned += runs[k].count;
+    if (int rc = ensure_stage(ctx, (size_t)(owned * sw))) return rc;
+    // gathered on the compute stream: after every queued pass, straight from
+    // the current plane (the pair layout is undone per word, no spare plane)
+    uint32_t* stage = ctx->region_stage;
+    for (int k = 0; k < nruns; ++k) {
+        const RowRun& r = runs[k];
+        HIP_CHECK(ctx, gol::launch_region_gather(ctx->plane[ctx->cur] + r.local_row * ctx->pitch, ctx->pitch,
+                                                 ctx->wwords, ctx->ilv, (int32_t)r.count, x0, w, stage, ctx->compute));
+        HIP_CHECK(ctx, hipMemcpy2DAsync(packed_out + r.win_row * host_pitch_words, (size_t)host_pitch_words * 4, stage,
+                                        (size_t)sw * 4, (size_t)sw * 4, (size_t)r.count, hipMemcpyDeviceToHost,
+                                        ctx->compute));
+        stage += r.count * sw;
+    }
+    HIP_CHECK(ctx, hipStreamSynchronize(ctx->compute));
+    return GOL_OK;
+}
+
+int gol_write_region(gol_ctx* ctx, int64_t x0, int64_t y0, int64_t w, int64_t h, const uint32_t* packed,
+                     int64_t host_pitch_words, int32_t mode) {
+    if (int rc = check_window(ctx, "gol_write_region", x0, y0, w, h, packed, host_pitch_words)) return rc;
+    if (mode != GOL_REGION_COPY && mode != GOL_REGION_OR && mode != GOL_REGION_XOR && mode != GOL_REGION_CLEAR)
+        return set_err(ctx, GOL_EINVAL, "gol_write_region: unknown mode %d", mode);
+    RowRun runs[2];
+    const int nruns = owned_runs(ctx, y0, h, runs);
+    if (nruns == 0) return GOL_OK;  // the window misses this shard
+    if (int rc = bind(ctx)) return rc;
+    const int64_t sw = (w + 31) / 32;
+    int64_t owned = 0;
+    for (int k = 0; k < nruns; ++k) owned += runs[k].count;
+    if (int rc = ensure_stage(ctx, (size_t)(owned * sw))) return rc;
+    // On the compute stream: after every queued pass and after the device
+    // copy of a snapshot in flight (gol_snapshot_async copies the board there
+    // first).  The epoch stays: neighbours pull this plane's edge rows again
+    // at the start of the next pass, after this stream's work.
+    uint32_t* stage = ctx->region_stage;
+    for (int k = 0; k < nruns; ++k) {
+        const RowRun& r = runs[k];
+        HIP_CHECK(ctx, hipMemcpy2DAsync(stage, (size_t)sw * 4, packed + r.win_row * host_pitch_words,
+                                        (size_t)host_pitch_words * 4, (size_t)sw * 4, (size_t)r.count,
+                                        hipMemcpyHostToDevice, ctx->compute));
+        HIP_CHECK(ctx, gol::launch_region_scatter(ctx->plane[ctx->cur] + r.local_row * ctx->pitch, ctx->pitch,
+                                                  ctx->wwords, ctx->width, ctx->ilv, (int32_t)r.count, x0, w, stage,
+                                                  mode, ctx->topology == GOL_TORUS, ctx->compute));
+        stage += r.count * sw;
+    }
+    HIP_CHECK(ctx, hipStreamSynchronize(ctx->compute));
+    return GOL_OK;
+}
+
+}  // extern "C"

@@ -7,7 +7,8 @@ Mirrors the reference package ``gameoflife`` (src/main/scala/gameoflife/):
 * ``engine``  -- ``GolEngine``: one libgol shard context (the backend worker
                  that replaces CellActor + NextStateCellGathererActor);
 * ``shard``   -- row-block decomposition and the multi-rank driver;
-* ``rules``   -- Life-like (birth, survive) masks incl. the reference's rules.
+* ``rules``   -- Life-like (birth, survive) masks incl. the reference's rules;
+* ``patterns`` -- RLE and O/. patterns as cell arrays for ``GolEngine.place``.
 
 ``engine`` (and everything that computes) needs ``lib/libgol.so``; it raises
 on import when the library is missing -- there is no CPU fallback.

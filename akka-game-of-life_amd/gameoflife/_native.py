@@ -86,6 +86,23 @@ class GolRuntimeInfo(ctypes.Structure):
     ]
 
 
+class GolCensusResult(ctypes.Structure):
+    _fields_ = [
+        ("population", ctypes.c_uint64),
+        ("min_x", ctypes.c_int64),
+        ("max_x", ctypes.c_int64),
+        ("min_y", ctypes.c_int64),
+        ("max_y", ctypes.c_int64),
+    ]
+
+
+# gol_write_region modes (include/gol.h GOL_REGION_*)
+GOL_REGION_COPY = 0
+GOL_REGION_OR = 1
+GOL_REGION_XOR = 2
+GOL_REGION_CLEAR = 3
+REGION_MODES = {"copy": GOL_REGION_COPY, "or": GOL_REGION_OR, "xor": GOL_REGION_XOR, "clear": GOL_REGION_CLEAR}
+
 _c = ctypes
 _vp = ctypes.c_void_p
 _u32p = ctypes.POINTER(ctypes.c_uint32)
@@ -145,6 +162,10 @@ _SIGNATURES = {
     "gol_profile_stats_read": (_c.c_int, [_vp, ctypes.POINTER(GolProfileStats)]),
     "gol_runtime_info_get": (_c.c_int, [ctypes.POINTER(GolRuntimeInfo)]),
     "gol_device_layout": (_c.c_int, [_c.c_int32, _c.c_int64, ctypes.POINTER(_c.c_int32)]),
+    "gol_census": (_c.c_int, [_vp, ctypes.POINTER(GolCensusResult)]),
+    "gol_read_region": (_c.c_int, [_vp, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_int64, _u32p, _c.c_int64]),
+    "gol_write_region": (_c.c_int, [_vp, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_int64, _u32p, _c.c_int64,
+                                    _c.c_int32]),
 }
 
 

@@ -12,6 +12,7 @@ import ctypes
 import numpy as np
 
 from . import _native as N
+from . import codec, patterns
 from .rules import Rule, rule_by_name
 
 
@@ -139,6 +140,56 @@ class GolEngine:
         s = ctypes.c_int(0)
         self._chk(N.lib.gol_get_cell(self._h, x, y, ctypes.byref(s)))
         return bool(s.value)
+
+    # -- patterns, windows and census (DESIGN.md "Patterns, windows and census")
+    def _census_raw(self) -> tuple[int, int, int, int, int]:
+        """(population, min_x, max_x, min_y, max_y) of this shard's rows, with
+        gol_census's sentinels when nothing is alive."""
+        r = N.GolCensusResult()
+        self._chk(N.lib.gol_census(self._h, ctypes.byref(r)))
+        return r.population, r.min_x, r.max_x, r.min_y, r.max_y
+
+    def census(self) -> dict:
+        """Live cells of this shard's rows and their bounding box, counted on
+        the device: {"population": n, "bbox": (min_x, min_y, max_x, max_y)},
+        inclusive global coordinates, bbox None when nothing is alive."""
+        return _census_dict(*self._census_raw())
+
+    def population(self) -> int:
+        return self._census_raw()[0]
+
+    def _read_region_into(self, x: int, y: int, w: int, h: int, packed: np.ndarray) -> None:
+        self._chk(N.lib.gol_read_region(self._h, x, y, w, h, packed.ctypes.data_as(N._u32p), packed.shape[1]))
+
+    def read_region(self, x: int, y: int, w: int, h: int) -> np.ndarray:
+        """The w x h window at (x, y) as a uint8 [h][w] cell array (a torus
+        wraps it).  Rows this shard does not own come back dead: the same call
+        on every shard of a board fills one buffer (ShardGroup.read_region)."""
+        packed = _window_buffer(w, h)
+        self._read_region_into(x, y, w, h, packed)
+        return codec.unpack(packed, w)
+
+    def _write_region_packed(self, x: int, y: int, w: int, h: int, packed: np.ndarray, mode: str) -> None:
+        if mode not in N.REGION_MODES:
+            raise ValueError(f"mode must be one of {sorted(N.REGION_MODES)}, not {mode!r}")
+        self._chk(N.lib.gol_write_region(self._h, x, y, w, h, packed.ctypes.data_as(N._u32p), packed.shape[1],
+                                         N.REGION_MODES[mode]))
+
+    def write_region(self, x: int, y: int, cells, mode: str = "copy") -> None:
+        """Combine a [h][w] cell array into the window at (x, y): mode "copy"
+        replaces the window, "or" adds the live cells, "xor" toggles them,
+        "clear" kills them.  The epoch stays; rows this shard does not own are
+        skipped."""
+        c = patterns.as_cells(cells)
+        self._write_region_packed(x, y, c.shape[1], c.shape[0], codec.pack(c), mode)
+
+    def set_cell(self, x: int, y: int, alive: bool = True) -> None:
+        self.write_region(x, y, np.ones((1, 1), dtype=np.uint8), "or" if alive else "clear")
+
+    def place(self, pattern, x: int, y: int, mode: str = "or") -> None:
+        """Drop a pattern -- RLE text, a list of O/. rows, or a cell array
+        (gameoflife.patterns) -- with its top-left cell at (x, y)."""
+        self.write_region(x, y, patterns.as_cells(pattern), mode)
 
     def checkpoint(self) -> np.ndarray:
         """gol_checkpoint into a new uint8 array (a bytes-like buffer: file
@@ -291,6 +342,39 @@ class ShardGroup:
     def snapshot(self) -> np.ndarray:
         return np.vstack([s.snapshot() for s in self.shards])
 
+    # -- patterns, windows and census: the same call on every shard ----------
+    def census(self) -> dict:
+        """The board's census: populations summed, boxes combined by min / max."""
+        raw = [s._census_raw() for s in self.shards]
+        return _census_dict(sum(r[0] for r in raw), min(r[1] for r in raw), max(r[2] for r in raw),
+                            min(r[3] for r in raw), max(r[4] for r in raw))
+
+    def population(self) -> int:
+        return sum(s._census_raw()[0] for s in self.shards)
+
+    def read_region(self, x: int, y: int, w: int, h: int) -> np.ndarray:
+        """The window, each shard filling the rows it owns of one buffer."""
+        packed = _window_buffer(w, h)
+        for s in self.shards:
+            s._read_region_into(x, y, w, h, packed)
+        return codec.unpack(packed, w)
+
+    def write_region(self, x: int, y: int, cells, mode: str = "copy") -> None:
+        c = patterns.as_cells(cells)
+        packed = codec.pack(c)
+        for s in self.shards:
+            s._write_region_packed(x, y, c.shape[1], c.shape[0], packed, mode)
+
+    def set_cell(self, x: int, y: int, alive: bool = True) -> None:
+        self.write_region(x, y, np.ones((1, 1), dtype=np.uint8), "or" if alive else "clear")
+
+    def place(self, pattern, x: int, y: int, mode: str = "or") -> None:
+        self.write_region(x, y, patterns.as_cells(pattern), mode)
+
+    def hash(self) -> int:
+        """The board's state hash: the shards' partials summed mod 2^64."""
+        return sum(s.hash() for s in self.shards) & 0xFFFFFFFFFFFFFFFF
+
     def close(self) -> None:
         if getattr(self, "_h", None) is not None and self._h.value:
             N.lib.gol_group_destroy(self._h)
@@ -307,6 +391,17 @@ class ShardGroup:
             self.close()
         except Exception:
             pass
+
+
+def _census_dict(population: int, min_x: int, max_x: int, min_y: int, max_y: int) -> dict:
+    bbox = (min_x, min_y, max_x, max_y) if population else None
+    return {"population": int(population), "bbox": bbox}
+
+
+def _window_buffer(w: int, h: int) -> np.ndarray:
+    """A zeroed packed buffer for a w x h window (gol_read_region fills the
+    rows a shard owns and leaves the others as they are)."""
+    return np.zeros((max(int(h), 1), max(codec.words_per_row(int(w)), 1)), dtype=np.uint32)
 
 
 class _HostBlock:

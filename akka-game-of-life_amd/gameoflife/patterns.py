@@ -1,0 +1,151 @@
+"""Life patterns as cell arrays: the run-length encoded (RLE) form pattern
+collections publish, and the O/. row form of tests/known_patterns.py.
+
+A pattern is a uint8 [h][w] array (1 = alive), the form GolEngine.place and
+write_region take.  The reference draws its initial state at random
+(BoardCreator.scala:23); a user who wants a glider gun at (x, y) starts here.
+"""
+from __future__ import annotations
+
+import re
+from typing import NamedTuple
+
+import numpy as np
+
+
+class Pattern(NamedTuple):
+    cells: np.ndarray   # uint8 [height][width]
+    width: int
+    height: int
+    rule: str | None    # the header's rule string, as written, if any
+
+
+_HEADER = re.compile(r"^\s*x\s*=\s*(\d+)\s*,\s*y\s*=\s*(\d+)\s*(?:,\s*rule\s*=\s*(\S+)\s*)?$", re.I)
+_TOKEN = re.compile(r"(\d*)([bo$!])")
+
+
+def parse_rle(text: str) -> Pattern:
+    """Parse an RLE pattern: `#` comment lines, an optional
+    `x = .., y = .., rule = ..` header, then runs `<count><tag>` with tag b
+    (dead), o (alive), $ (end of row; a count skips rows) and ! (end).  The
+    header's extents size the array when present (the body must fit them);
+    otherwise the body's own extents do.  Anything else raises ValueError."""
+    width = height = None
+    rule = None
+    body = []
+    for line in text.splitlines():
+        s = line.strip()
+        if not s or s.startswith("#"):
+            continue
+        if not body and width is None:
+            m = _HEADER.match(s)
+            if m:
+                width, height, rule = int(m.group(1)), int(m.group(2)), m.group(3)
+                continue
+        body.append(s)
+    data = "".join("".join(body).split())
+    end = data.find("!")
+    if end >= 0:
+        data = data[:end + 1]
+    live = []          # (x, y) of live cells
+    x = y = 0
+    xmax = 0           # widest row, dead runs included
+    pos = 0
+    while pos < len(data):
+        m = _TOKEN.match(data, pos)
+        if not m:
+            raise ValueError(f"RLE: unexpected {data[pos:pos + 8]!r} at offset {pos}")
+        pos = m.end()
+        n = int(m.group(1)) if m.group(1) else 1
+        tag = m.group(2)
+        if n == 0:
+            raise ValueError("RLE: zero run count")
+        if tag == "b":
+            x += n
+        elif tag == "o":
+            live.extend((x + k, y) for k in range(n))
+            x += n
+        elif tag == "$":
+            xmax = max(xmax, x)
+            x = 0
+            y += n
+        else:  # "!"
+            if m.group(1):
+                raise ValueError("RLE: a run count before '!'")
+            break
+    xmax = max(xmax, x)
+    rows = y + 1
+    if width is None:
+        width, height = max(xmax, 1), rows
+    elif xmax > width or any(cy >= height for _, cy in live):
+        raise ValueError(f"RLE: the body does not fit the header's {width} x {height}")
+    if width < 1 or height < 1:
+        raise ValueError("RLE: empty extents")
+    cells = np.zeros((height, width), dtype=np.uint8)
+    for cx, cy in live:
+        cells[cy, cx] = 1
+    return Pattern(cells, width, height, rule)
+
+
+def to_rle(cells, rule: str | None = "B3/S23") -> str:
+    """RLE text of a cell array, with the header that restores its extents
+    (trailing dead columns and rows are not written in the body)."""
+    c = np.asarray(cells, dtype=np.uint8) & 1
+    if c.ndim != 2 or c.shape[0] < 1 or c.shape[1] < 1:
+        raise ValueError("to_rle takes a non-empty [h][w] cell array")
+    h, w = c.shape
+    tokens = []
+    pending = 0  # row ends not yet written
+    for row in c:
+        alive = np.flatnonzero(row)
+        if alive.size:
+            if pending:
+                tokens.append(("$", pending))
+                pending = 0
+            r = row[:alive[-1] + 1]
+            cuts = np.flatnonzero(np.diff(r)) + 1
+            for seg in np.split(r, cuts):
+                tokens.append(("o" if seg[0] else "b", len(seg)))
+        pending += 1
+    out = [f"x = {w}, y = {h}" + (f", rule = {rule}" if rule else "")]
+    line = ""
+    for tag, n in tokens + [("!", 1)]:
+        t = (str(n) if n > 1 else "") + tag
+        if len(line) + len(t) > 70:
+            out.append(line)
+            line = ""
+        line += t
+    out.append(line)
+    return "\n".join(out) + "\n"
+
+
+def from_rows(rows) -> np.ndarray:
+    """Cell array of a list of strings, `O` alive and `.` dead (short rows are
+    padded with dead cells)."""
+    rows = list(rows)
+    if not rows:
+        raise ValueError("from_rows takes at least one row")
+    w = max(max(len(r) for r in rows), 1)
+    cells = np.zeros((len(rows), w), dtype=np.uint8)
+    for y, r in enumerate(rows):
+        for x, ch in enumerate(r):
+            if ch == "O":
+                cells[y, x] = 1
+            elif ch != ".":
+                raise ValueError(f"from_rows: unexpected {ch!r} in row {y}")
+    return cells
+
+
+def as_cells(pattern) -> np.ndarray:
+    """A pattern in any accepted form -- RLE text, a list of O/. rows, a
+    Pattern, or a cell array -- as a uint8 [h][w] array."""
+    if isinstance(pattern, Pattern):
+        return pattern.cells
+    if isinstance(pattern, str):
+        return parse_rle(pattern).cells
+    if isinstance(pattern, (list, tuple)) and pattern and all(isinstance(r, str) for r in pattern):
+        return from_rows(pattern)
+    c = np.asarray(pattern, dtype=np.uint8) & 1
+    if c.ndim != 2 or c.shape[0] < 1 or c.shape[1] < 1:
+        raise ValueError("a pattern is a non-empty [h][w] cell array")
+    return c

@@ -51,7 +51,9 @@ extern "C" {
 /* 2 (round 5): the state hash became a function of the cells alone (see the
  * header comment); the values of tori with an even word count are unchanged,
  * those of row-major boards (clipped, odd word counts) differ from version 1.
- * The entry points and structs are those of version 1. */
+ * The entry points and structs are those of version 1.  gol_census,
+ * gol_read_region and gol_write_region were added without a new version:
+ * additive entry points change nothing a version-2 caller relies on. */
 #define GOL_ABI_VERSION 2
 
 /* Return codes. */
@@ -228,6 +230,67 @@ void gol_host_free(void* p);
 /* State of one cell of the shard at the current epoch (0/1).  Replaces the
  * GetStateFromEpoch -> StateForEpoch exchange (CellActor.scala:71-77). */
 int gol_get_cell(gol_ctx* ctx, int64_t x, int64_t y, int* state);
+
+/* Census of the shard's rows, counted on the device in one pass over the
+ * plane: the live cells and their bounding box in global coordinates
+ * (inclusive; plain coordinate minima and maxima, not wrap-aware).  Replaces
+ * reading a population off the LoggerActor's board dump
+ * (LoggerActor.scala:30-46), which a host can only do after gol_snapshot has
+ * shipped every row.  Every stored cell of the shard's rows counts -- on a
+ * GOL_REF_CLIPPED board that includes the cells outside the visible extent.
+ * A shard with no live cell reports population = 0, min_x = min_y = INT64_MAX
+ * and max_x = max_y = -1, so shards combine by sum, elementwise min and
+ * elementwise max.  Synchronises. */
+typedef struct gol_census_result {
+    uint64_t population;                 /* live cells of this shard's rows            */
+    int64_t min_x, max_x, min_y, max_y;  /* bounding box of the live cells, global
+                                            coordinates, inclusive                     */
+} gol_census_result;
+int gol_census(gol_ctx* ctx, gol_census_result* out);
+
+/* Windows: read or change a w x h block of cells without moving the board.
+ * gol_read_region replaces the CellStateMsg stream of the cells of a window
+ * to the LoggerActor (CellActor.scala:89, LoggerActor.scala:30-46);
+ * gol_write_region replaces the per-cell initialState a BoardCreator hands to
+ * the cells it places (BoardCreator.scala:65-70) -- at any epoch, and without
+ * gol_load's upload of every row.
+ *
+ * Window buffers use the host layout above: window row i, window column k is
+ * bit k % 32 of word k / 32 of row i; rows are host_pitch_words apart,
+ * host_pitch_words >= ceil(w / 32).  On write the bits at k >= w of a row's
+ * last word are ignored; on read they are written as zero (words of a row
+ * past ceil(w / 32) are not touched).
+ *
+ * The window: 1 <= w <= width, 1 <= h <= height, 0 <= x0 < width,
+ * 0 <= y0 < height.  Window cell (k, i) is board cell ((x0 + k) mod width,
+ * (y0 + i) mod height) of a torus.  On GOL_REF_CLIPPED the window must lie
+ * inside the stored board: x0 + w <= width and y0 + h <= height.
+ *
+ * Null pointers, an unknown mode, a short pitch and windows out of range
+ * return GOL_EINVAL with a message (gol_last_error) before any device work is
+ * queued.
+ *
+ * Window rows whose board row is not one of the shard's rows
+ * [row0, row0 + rows) are skipped: a write does not touch them, a read leaves
+ * those rows of packed_out as they are.  A sharded caller therefore issues
+ * the same call with the same buffer on every shard -- of an in-process
+ * group, a loopback ring or an RCCL ring -- and gets the whole window; a
+ * window that misses the shard altogether returns GOL_OK.
+ *
+ * gol_write_region combines the pattern into the window under `mode` and does
+ * not change the epoch.  It is ordered on the context's compute stream after
+ * every queued pass and after the device copy of a snapshot in flight; both
+ * calls synchronise before they return, as gol_snapshot and gol_get_cell do.
+ * Both are valid with a communicator or group attached: halo rows are
+ * exchanged again at every pass.  Bits at x >= width stay zero. */
+#define GOL_REGION_COPY  0   /* window := pattern           */
+#define GOL_REGION_OR    1   /* window |= pattern           */
+#define GOL_REGION_XOR   2   /* window ^= pattern           */
+#define GOL_REGION_CLEAR 3   /* window &= ~pattern          */
+int gol_read_region(gol_ctx* ctx, int64_t x0, int64_t y0, int64_t w, int64_t h,
+                    uint32_t* packed_out, int64_t host_pitch_words);
+int gol_write_region(gol_ctx* ctx, int64_t x0, int64_t y0, int64_t w, int64_t h,
+                     const uint32_t* packed, int64_t host_pitch_words, int32_t mode);
 
 /* Shard checkpoint = {header with epoch + geometry, packed board}.  Replaces
  * the reference's recovery state (initialState kept by the frontend,
