@@ -322,7 +322,7 @@ int gol_create(gol_ctx** out, const gol_config* cfg) {
     }
     // Load every step kernel instance this context can launch, now: the HIP
     // runtime loads a code object on the first use of one of its kernels, and
-    // each pass depth lives in its own code object (gol_step_g<G>.hip), so the
+    // each pass depth lives in its own code object (gol_step.hip, built per depth), so the
     // first gol_step that plans a new depth would otherwise stall inside the
     // caller's timed region (gol_set_tuning repeats this when it changes the
     // lane width).
@@ -529,17 +529,9 @@ int gol_occupancy(gol_ctx* ctx, int32_t gens_per_pass, int32_t* waves_per_cu, in
     if (gens_per_pass < 1 || gens_per_pass > gol::kMaxGensPerPass)
         return set_err(ctx, GOL_EINVAL, "gens_per_pass out of range");
     if (int rc = bind(ctx)) return rc;
-    const bool clipped = ctx->topology == GOL_REF_CLIPPED;
-    const bool life = !clipped && ctx->birth == GOL_RULE_LIFE_BIRTH && ctx->survive == GOL_RULE_LIFE_SURVIVE;
-    const int vec = lane_words(ctx, gens_per_pass);
-    const int blocks =
-        gol::resident_blocks_per_cu(vec, gens_per_pass, life, false, clipped, ctx->ilv);
-    if (waves_per_cu) *waves_per_cu = blocks * gol::kWavesPerWG;
-    if (strip_words)
-        *strip_words = gol::whole_row_fits(vec, gens_per_pass, life, clipped, ctx->ilv, ctx->topology == GOL_TORUS,
-                                           ctx->wwords)
-                           ? gol::kWaveLanes * vec  // whole-row waves: no halo lanes
-                           : gol::strip_words(vec, gens_per_pass);
+    const gol::StepInstance k = step_instance(ctx, gens_per_pass, false);
+    if (waves_per_cu) *waves_per_cu = gol::resident_blocks_per_cu(k) * gol::kWavesPerWG;
+    if (strip_words) *strip_words = gol::strip_words(k);
     return GOL_OK;
 }
 

@@ -198,7 +198,10 @@ int clear_slots(gol_ctx* ctx, uint32_t gens);
 // the accumulators cleared again; synchronises.
 int read_hashes(gol_ctx* ctx, uint32_t gens, uint64_t* out);
 int lane_words(const gol_ctx* ctx, int gens);
-int64_t resident_waves(const gol_ctx* ctx, int vec, int gens, bool life, bool hash, bool clipped);
+// The kernel instance a pass of `gens` generations runs on this context: the
+// one place that derives it (and so a pass's strip width, gol::strip_words).
+gol::StepInstance step_instance(const gol_ctx* ctx, int gens, bool hashed);
+int64_t resident_waves(const gol_ctx* ctx, const gol::StepInstance& k);
 // Load every step kernel instance the context can launch at its current
 // tuning (the occupancy query of an instance loads its code object).
 void preload_instances(gol_ctx* ctx);

@@ -1,6 +1,7 @@
 // gol_kernels.h -- internal interface between the C-ABI host layer
 // (gol_capi.cpp and the units gol_ctx.h lists) and the gfx950 kernels
-// (gol_stencil.h, gol_step_g<G>.hip, gol_misc.hip, gol_region.hip).  Not
+// (gol_stencil.h, gol_step.hip -- built once per pass depth --, gol_misc.hip,
+// gol_region.hip).  Not
 // installed.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -99,7 +100,6 @@ struct StepParams {
     int32_t strips;            // column strips per row
     int32_t wrap_x;            // torus in x
     int32_t wrap_y;            // unsharded torus: local rows wrap modulo `rows`
-    int32_t whole_row;         // one strip = the whole torus row (kWholeRow*: wave-rotate neighbours, no halo lanes)
     int64_t halo_stride;       // words between halo rows (0: one row repeated)
     uint32_t birth;
     uint32_t survive;
@@ -107,15 +107,14 @@ struct StepParams {
     unsigned long long* clk;   // launch clock probe slot (kClockSlotWords u64), or null (gol_stencil.h clock_probe_*)
 };
 
+using StepKernel = void (*)(StepParams);  // every step kernel's type
+
 // Per launch: kClockSubSlots sub-slots one 64-B line apart, each summing
 // core-clock ticks and 100 MHz reference ticks of the sampled workgroups.
 constexpr int kClockSubSlots = 64;
 constexpr int kClockSubWords = 8;
 constexpr int kClockSampleEvery = 4;
 constexpr int kClockSlotWords = kClockSubSlots * kClockSubWords;
-
-// Strip geometry of a launch: words covered per wave.
-int strip_words(int vec, int gens);
 
 // Whole-row waves: a B3/S23 torus in the pair layout whose row is exactly one
 // wave of 2-word lanes (64 pairs, 4096 columns -- BASELINE.json configs[1])
@@ -129,18 +128,29 @@ inline bool whole_row_fits(int vec, int gens, bool life, bool clipped, int ilv, 
            wwords == (int64_t)kWaveLanes * kWholeRowVec;
 }
 
-// vec: words per lane (1, 2 or 4); gens: generations per pass; life: B3/S23
-// fast path (torus only); hash: fuse the per-generation state hash; clipped:
-// reference geometry; ilv: the plane's interleave (1 row-major, 2 pairs;
-// vec a multiple of it).  Multi-generation passes at vec <= 2 run the
-// horizontal-first kernel, at vec = 4 the vertical-first one.
-hipError_t launch_step(const StepParams& p, int vec, int gens, bool life, bool hash, bool clipped, int ilv,
-                       int grid_x, int grid_y, hipStream_t stream);
+// The step kernel instance of a pass.  vec: words per lane (1, 2 or 4); gens:
+// generations per pass; ilv: the plane's interleave (1 row-major, 2 pairs; vec
+// a multiple of it); life: B3/S23 fast path (torus only); hash: fuse the
+// per-generation state hash; clipped: reference geometry; whole_row: one strip
+// is the whole torus row (whole_row_fits).  Multi-generation passes at
+// vec <= 2 run the horizontal-first kernel, at vec = 4 the vertical-first one.
+struct StepInstance {
+    int vec, gens, ilv;
+    bool life, hash, clipped, whole_row;
+};
 
-// Resident 256-thread workgroups per CU of the step kernel instance a launch
-// with these parameters uses (hipOccupancyMaxActiveBlocksPerMultiprocessor);
-// 0 if unknown.
-int resident_blocks_per_cu(int vec, int gens, bool life, bool hash, bool clipped, int ilv);
+// Strip geometry of a launch: words covered per wave (multi-generation strips
+// keep one halo lane per side, whole-row waves none).
+inline int strip_words(const StepInstance& k) {
+    return (k.gens == 1 || k.whole_row ? kWaveLanes : kWaveLanes - 2) * k.vec;
+}
+
+// hipErrorInvalidValue for an instance that is not built.
+hipError_t launch_step(const StepParams& p, const StepInstance& k, int grid_x, int grid_y, hipStream_t stream);
+
+// Resident 256-thread workgroups per CU of the instance
+// (hipOccupancyMaxActiveBlocksPerMultiprocessor); 0 if unknown or not built.
+int resident_blocks_per_cu(const StepInstance& k);
 
 // Seeded board in the device layout (ilv: words per interleave group).
 hipError_t launch_seed(uint32_t* plane, int64_t pitch, int32_t wwords, int64_t width,

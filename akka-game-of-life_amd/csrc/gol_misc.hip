@@ -1,5 +1,5 @@
 // gol_misc.hip -- board seeding, standalone state hash, the cross-lane self
-// test, and the launch dispatcher over pass depths.
+// test, and the step launch over the per-depth kernel objects.
 #include <algorithm>
 
 #include "gol_layout.h"
@@ -120,43 +120,36 @@ __global__ void selftest_kernel(const uint32_t* in, uint32_t* out) {
 
 }  // namespace
 
-int strip_words(int vec, int gens) { return (gens == 1 ? kWaveLanes : kWaveLanes - 2) * vec; }
+namespace {
 
-hipError_t launch_step(const StepParams& p, int vec, int gens, bool life, bool hash, bool clipped, int ilv,
-                       int grid_x, int grid_y, hipStream_t stream) {
-    switch (gens) {
-        case 1: return launch_step_g1(p, vec, life, hash, clipped, ilv, grid_x, grid_y, stream);
-        case 2: return launch_step_g2(p, vec, life, hash, clipped, ilv, grid_x, grid_y, stream);
-        case 3: return launch_step_g3(p, vec, life, hash, clipped, ilv, grid_x, grid_y, stream);
-        case 4: return launch_step_g4(p, vec, life, hash, clipped, ilv, grid_x, grid_y, stream);
-        case 5: return launch_step_g5(p, vec, life, hash, clipped, ilv, grid_x, grid_y, stream);
-        case 6: return launch_step_g6(p, vec, life, hash, clipped, ilv, grid_x, grid_y, stream);
-        case 7: return launch_step_g7(p, vec, life, hash, clipped, ilv, grid_x, grid_y, stream);
-        case 8: return launch_step_g8(p, vec, life, hash, clipped, ilv, grid_x, grid_y, stream);
-        case 9: return launch_step_g9(p, vec, life, hash, clipped, ilv, grid_x, grid_y, stream);
-        case 10: return launch_step_g10(p, vec, life, hash, clipped, ilv, grid_x, grid_y, stream);
-        case 11: return launch_step_g11(p, vec, life, hash, clipped, ilv, grid_x, grid_y, stream);
-        case 12: return launch_step_g12(p, vec, life, hash, clipped, ilv, grid_x, grid_y, stream);
-        default: return hipErrorInvalidValue;
-    }
+// The kernel of instance `k`, from the per-depth objects (gol_step.hip); null
+// if the instance is not built.
+template <int... I>
+StepKernel step_kernel_of(const StepInstance& k, std::integer_sequence<int, I...>) {
+    static constexpr StepKernel (*kAtDepth[])(const StepInstance&) = {&step_kernel_at<I + 1>...};
+    return k.gens >= 1 && k.gens <= kMaxGensPerPass ? kAtDepth[k.gens - 1](k) : nullptr;
+}
+StepKernel step_kernel_of(const StepInstance& k) {
+    return step_kernel_of(k, std::make_integer_sequence<int, kMaxGensPerPass>{});
 }
 
-int resident_blocks_per_cu(int vec, int gens, bool life, bool hash, bool clipped, int ilv) {
-    switch (gens) {
-        case 1: return blocks_step_g1(vec, life, hash, clipped, ilv);
-        case 2: return blocks_step_g2(vec, life, hash, clipped, ilv);
-        case 3: return blocks_step_g3(vec, life, hash, clipped, ilv);
-        case 4: return blocks_step_g4(vec, life, hash, clipped, ilv);
-        case 5: return blocks_step_g5(vec, life, hash, clipped, ilv);
-        case 6: return blocks_step_g6(vec, life, hash, clipped, ilv);
-        case 7: return blocks_step_g7(vec, life, hash, clipped, ilv);
-        case 8: return blocks_step_g8(vec, life, hash, clipped, ilv);
-        case 9: return blocks_step_g9(vec, life, hash, clipped, ilv);
-        case 10: return blocks_step_g10(vec, life, hash, clipped, ilv);
-        case 11: return blocks_step_g11(vec, life, hash, clipped, ilv);
-        case 12: return blocks_step_g12(vec, life, hash, clipped, ilv);
-        default: return 0;
+}  // namespace
+
+hipError_t launch_step(const StepParams& p, const StepInstance& k, int grid_x, int grid_y, hipStream_t stream) {
+    const StepKernel kernel = step_kernel_of(k);
+    if (!kernel) return hipErrorInvalidValue;
+    return launch_kernel(kernel, dim3(grid_x, grid_y), dim3(kWaveLanes * kWavesPerWG), stream, p);
+}
+
+int resident_blocks_per_cu(const StepInstance& k) {
+    const StepKernel kernel = step_kernel_of(k);
+    int n = 0;
+    if (!kernel) return 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kernel, kWaveLanes * kWavesPerWG, 0) != hipSuccess) {
+        (void)hipGetLastError();  // the failed query's own status: reported as 0 (unknown), not left pending
+        return 0;
     }
+    return n;
 }
 
 hipError_t launch_seed(uint32_t* plane, int64_t pitch, int32_t wwords, int64_t width, int64_t grow0, int32_t rows,

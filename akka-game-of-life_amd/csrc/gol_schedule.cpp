@@ -299,25 +299,35 @@ int lane_words(const gol_ctx* ctx, int gens) {
     return ok2 || ctx->ilv == 2 ? 2 : 1;
 }
 
+gol::StepInstance step_instance(const gol_ctx* ctx, int gens, bool hashed) {
+    gol::StepInstance k{};
+    k.vec = lane_words(ctx, gens);
+    k.gens = gens;
+    k.ilv = ctx->ilv;
+    k.life = life_torus(ctx);
+    k.hash = hashed;
+    k.clipped = ctx->topology == GOL_REF_CLIPPED;
+    k.whole_row =
+        gol::whole_row_fits(k.vec, gens, k.life, k.clipped, k.ilv, ctx->topology == GOL_TORUS, ctx->wwords);
+    return k;
+}
+
 // Resident waves on the whole GPU for a launch (cached occupancy query).
-int64_t resident_waves(const gol_ctx* ctx, int vec, int gens, bool life, bool hash, bool clipped) {
-    const int key = ((((vec * 16 + gens) * 2 + (life ? 1 : 0)) * 2 + (hash ? 1 : 0)) * 2 + (clipped ? 1 : 0)) * 8 +
-                    ctx->ilv;
+int64_t resident_waves(const gol_ctx* ctx, const gol::StepInstance& k) {
+    const int key = (((((k.vec * 16 + k.gens) * 2 + k.life) * 2 + k.hash) * 2 + k.clipped) * 2 + k.whole_row) * 8 +
+                    k.ilv;
     auto it = ctx->occupancy_cache.find(key);
     if (it != ctx->occupancy_cache.end()) return it->second;
-    const int blocks = gol::resident_blocks_per_cu(vec, gens, life, hash, clipped, ctx->ilv);
-    const int64_t waves = (int64_t)blocks * gol::kWavesPerWG * ctx->num_cus;
+    const int64_t waves = (int64_t)gol::resident_blocks_per_cu(k) * gol::kWavesPerWG * ctx->num_cus;
     ctx->occupancy_cache[key] = waves;
     return waves;
 }
 
 void preload_instances(gol_ctx* ctx) {
-    const bool clipped = ctx->topology == GOL_REF_CLIPPED;
-    const bool life = !clipped && ctx->birth == GOL_RULE_LIFE_BIRTH && ctx->survive == GOL_RULE_LIFE_SURVIVE;
     // unbuilt instances (16-byte generic / clipped lanes deeper than
     // kMaxGensVec4Generic, gol_stencil.h kBuilt) report 0 blocks without a load
     for (int G = 1; G <= gol::kMaxGensPerPass; ++G)
-        for (int h = 0; h < 2; ++h) (void)resident_waves(ctx, lane_words(ctx, G), G, life, h != 0, clipped);
+        for (int h = 0; h < 2; ++h) (void)resident_waves(ctx, step_instance(ctx, G, h != 0));
 }
 
 // Launch one pass of `gens` generations over local row ranges [lo0,hi0)
@@ -343,16 +353,12 @@ int launch_ranges(gol_ctx* ctx, int gens, const uint32_t* cur, uint32_t* nxt, co
     p.width = ctx->width;
     p.wwords = ctx->wwords;
     p.rows = geom ? geom->rows : (int32_t)ctx->rows;
-    const int vec = lane_words(ctx, gens);
-    const bool clipped = ctx->topology == GOL_REF_CLIPPED;
-    const bool life = !clipped && ctx->birth == GOL_RULE_LIFE_BIRTH && ctx->survive == GOL_RULE_LIFE_SURVIVE;
-    p.whole_row = gol::whole_row_fits(vec, gens, life, clipped, ctx->ilv, ctx->topology == GOL_TORUS, ctx->wwords)
-                      ? 1 : 0;
-    const int sw = p.whole_row ? gol::kWaveLanes * vec : gol::strip_words(vec, gens);
+    const gol::StepInstance k = step_instance(ctx, gens, slots != nullptr);
+    const int sw = gol::strip_words(k);
     p.strips = (int32_t)((ctx->wwords + sw - 1) / sw);
     int64_t maxlen = 0;
     for (int k = 0; k < n; ++k) maxlen = std::max<int64_t>(maxlen, hi[k] - lo[k]);
-    const int64_t resident = (n == 1 && gens > 1) ? resident_waves(ctx, vec, gens, life, slots != nullptr, clipped) : 0;
+    const int64_t resident = (n == 1 && gens > 1) ? resident_waves(ctx, k) : 0;
     int band = pick_band(ctx, maxlen, p.strips, gens, resident);
     const int small = n == 1 ? small_board_band(ctx, maxlen, p.strips, gens, band, resident) : 0;
     if (small > 0) band = small;
@@ -398,7 +404,7 @@ int launch_ranges(gol_ctx* ctx, int gens, const uint32_t* cur, uint32_t* nxt, co
         }
         HIP_CHECK(ctx, hipEventRecord(ev->start, stream));
     }
-    HIP_CHECK(ctx, gol::launch_step(p, vec, gens, life, slots != nullptr, clipped, ctx->ilv, gx, 1, stream));
+    HIP_CHECK(ctx, gol::launch_step(p, k, gx, 1, stream));
     if (ev) {
         HIP_CHECK(ctx, hipEventRecord(ev->stop, stream));
         if (prof_kind == kProfMain) ctx->prof_gens += (uint64_t)gens;
@@ -490,10 +496,13 @@ int depth_cap(const gol_ctx* ctx) {
 static bool small_board(const gol_ctx* ctx) {
     if (sharded(ctx) || ctx->group || !life_torus(ctx) || depth_cap(ctx) < 10) return false;
     const int G = 10;
-    const int vec = lane_words(ctx, G);
-    const int sw = gol::strip_words(vec, G);
+    gol::StepInstance k = step_instance(ctx, G, true);
+    const int64_t resident = resident_waves(ctx, k);
+    // sized with halo-lane strips even where the pass runs whole-row waves:
+    // whether that should change needs a measurement (small_board)
+    k.whole_row = false;
+    const int sw = gol::strip_words(k);
     const int strips = (int)((ctx->wwords + sw - 1) / sw);
-    const int64_t resident = resident_waves(ctx, vec, G, true, true, false);
     const int band = pick_band(ctx, ctx->rows, strips, G, resident);
     return small_board_band(ctx, ctx->rows, strips, G, band, resident) > 0;
 }
@@ -512,7 +521,7 @@ std::vector<int> plan_passes(const gol_ctx* ctx, uint32_t n, bool hashed) {
         for (uint32_t g = 0; g < n; g += plan.back()) plan.push_back((int)std::min<uint32_t>(cap, n - g));
         return plan;
     }
-    const int sw = gol::strip_words(lane_words(ctx, 6), 6);
+    const int sw = gol::strip_words(step_instance(ctx, 6, hashed));
     const bool wide = (ctx->wwords + sw - 1) / sw >= 32;
     const double* cost = kPassCost[hashed && !small_board(ctx) ? 1 : 0][wide ? 1 : 0];
     std::vector<double> best(n + 1, 0.0);

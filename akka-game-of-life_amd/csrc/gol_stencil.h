@@ -1156,45 +1156,23 @@ __global__ __launch_bounds__(kWaveLanes* kWavesPerWG) void multistep_hg_kernel(c
 template <int VEC, int G, bool LIFE, bool CLIPPED>
 constexpr bool kBuilt = G == 1 || VEC <= 2 || (LIFE && !CLIPPED) || G <= kMaxGensVec4Generic;
 
+// The kernel of one instance, or null: not built, or `whole_row` where the
+// instance has no whole-row kernel (the host layer asks for neither).
 template <int VEC, int G, bool LIFE, bool HASH, bool CLIPPED, int ILV>
-hipError_t launch_one(const StepParams& p, int gx, int gy, hipStream_t st) {
-    const dim3 grid(gx, gy), block(kWaveLanes * kWavesPerWG);
-    if constexpr (G == 1) {
-        return launch_kernel(step_kernel<VEC, LIFE, HASH, CLIPPED, ILV>, grid, block, st, p);
-    } else if constexpr (!kBuilt<VEC, G, LIFE, CLIPPED>) {
-        return hipErrorInvalidValue;
+StepKernel kernel_one(bool whole_row) {
+    if constexpr (!kBuilt<VEC, G, LIFE, CLIPPED>) {
+        return nullptr;
+    } else if constexpr (VEC == kWholeRowVec && G == kWholeRowGens && LIFE && !CLIPPED && ILV == 2) {
+        return whole_row ? multistep_hg_kernel<VEC, G, LIFE, HASH, CLIPPED, ILV, true>
+                         : multistep_hg_kernel<VEC, G, LIFE, HASH, CLIPPED, ILV>;
+    } else if (whole_row) {
+        return nullptr;
+    } else if constexpr (G == 1) {
+        return step_kernel<VEC, LIFE, HASH, CLIPPED, ILV>;
     } else if constexpr (VEC <= 2) {
-        if constexpr (VEC == kWholeRowVec && G == kWholeRowGens && LIFE && !CLIPPED && ILV == 2) {
-            if (p.whole_row)
-                return launch_kernel(multistep_hg_kernel<VEC, G, LIFE, HASH, CLIPPED, ILV, true>, grid, block, st, p);
-        }
-        if (p.whole_row) return hipErrorInvalidValue;  // no whole-row instance (checked by the host layer)
-        return launch_kernel(multistep_hg_kernel<VEC, G, LIFE, HASH, CLIPPED, ILV>, grid, block, st, p);
+        return multistep_hg_kernel<VEC, G, LIFE, HASH, CLIPPED, ILV>;
     } else {
-        if (p.whole_row) return hipErrorInvalidValue;
-        return launch_kernel(multistep_kernel<VEC, G, LIFE, HASH, CLIPPED, ILV>, grid, block, st, p);
-    }
-}
-
-// Resident 256-thread workgroups per CU for a kernel instance (occupancy API).
-template <int VEC, int G, bool LIFE, bool HASH, bool CLIPPED, int ILV>
-int blocks_one() {
-    auto query = [](auto kernel) {
-        int n = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kernel, kWaveLanes * kWavesPerWG, 0) != hipSuccess) {
-            (void)hipGetLastError();  // the failed query's own status: reported as 0 (unknown), not left pending
-            return 0;
-        }
-        return n;
-    };
-    if constexpr (G == 1) {
-        return query(step_kernel<VEC, LIFE, HASH, CLIPPED, ILV>);
-    } else if constexpr (!kBuilt<VEC, G, LIFE, CLIPPED>) {
-        return 0;
-    } else if constexpr (VEC <= 2) {
-        return query(multistep_hg_kernel<VEC, G, LIFE, HASH, CLIPPED, ILV>);
-    } else {
-        return query(multistep_kernel<VEC, G, LIFE, HASH, CLIPPED, ILV>);
+        return multistep_kernel<VEC, G, LIFE, HASH, CLIPPED, ILV>;
     }
 }
 
@@ -1219,70 +1197,31 @@ auto dispatch_kind(bool life, bool hash, bool clipped, int ilv, F&& f) {
     return hash ? f(N{}, T{}, N{}, I1{}) : f(N{}, N{}, N{}, I1{});
 }
 
-template <int VEC, int G>
-int blocks_variant(bool life, bool hash, bool clipped, int ilv) {
-    if (VEC % ilv != 0) return 0;
-    return dispatch_kind<VEC>(life, hash, clipped, ilv, [&](auto L, auto H, auto C, auto I) {
-        return blocks_one<VEC, G, decltype(L)::value, decltype(H)::value, decltype(C)::value, decltype(I)::value>();
-    });
-}
-
+// The kernel of instance `k` at depth G (k.gens is not looked at).
 template <int G>
-int blocks_gens(int vec, bool life, bool hash, bool clipped, int ilv) {
-    switch (vec) {
-        case 4: return blocks_variant<4, G>(life, hash, clipped, ilv);
-        case 2: return blocks_variant<2, G>(life, hash, clipped, ilv);
-        default: return blocks_variant<1, G>(life, hash, clipped, ilv);
-    }
-}
-
-template <int VEC, int G>
-hipError_t launch_variant(const StepParams& p, bool life, bool hash, bool clipped, int ilv, int gx, int gy,
-                          hipStream_t st) {
-    if (VEC % ilv != 0) return hipErrorInvalidValue;  // checked by the host layer
-    return dispatch_kind<VEC>(life, hash, clipped, ilv, [&](auto L, auto H, auto C, auto I) {
-        return launch_one<VEC, G, decltype(L)::value, decltype(H)::value, decltype(C)::value, decltype(I)::value>(
-            p, gx, gy, st);
-    });
-}
-
-template <int G>
-hipError_t launch_gens(const StepParams& p, int vec, bool life, bool hash, bool clipped, int ilv, int gx, int gy,
-                       hipStream_t st) {
-    switch (vec) {
-        case 4: return launch_variant<4, G>(p, life, hash, clipped, ilv, gx, gy, st);
-        case 2: return launch_variant<2, G>(p, life, hash, clipped, ilv, gx, gy, st);
-        case 1: return launch_variant<1, G>(p, life, hash, clipped, ilv, gx, gy, st);
-        default: return hipErrorInvalidValue;
+StepKernel kernel_at_depth(const StepInstance& k) {
+    auto of_vec = [&](auto V) -> StepKernel {
+        constexpr int VEC = decltype(V)::value;
+        if (VEC % k.ilv != 0) return nullptr;  // checked by the host layer
+        return dispatch_kind<VEC>(k.life, k.hash, k.clipped, k.ilv, [&](auto L, auto H, auto C, auto I) {
+            return kernel_one<VEC, G, decltype(L)::value, decltype(H)::value, decltype(C)::value, decltype(I)::value>(
+                k.whole_row);
+        });
+    };
+    switch (k.vec) {
+        case 4: return of_vec(std::integral_constant<int, 4>{});
+        case 2: return of_vec(std::integral_constant<int, 2>{});
+        case 1: return of_vec(std::integral_constant<int, 1>{});
+        default: return nullptr;
     }
 }
 
 }  // namespace dev
 
-// Defined one per translation unit (gol_step_g<G>.hip).
-hipError_t launch_step_g1(const StepParams&, int, bool, bool, bool, int, int, int, hipStream_t);
-hipError_t launch_step_g2(const StepParams&, int, bool, bool, bool, int, int, int, hipStream_t);
-hipError_t launch_step_g3(const StepParams&, int, bool, bool, bool, int, int, int, hipStream_t);
-hipError_t launch_step_g4(const StepParams&, int, bool, bool, bool, int, int, int, hipStream_t);
-hipError_t launch_step_g5(const StepParams&, int, bool, bool, bool, int, int, int, hipStream_t);
-hipError_t launch_step_g6(const StepParams&, int, bool, bool, bool, int, int, int, hipStream_t);
-hipError_t launch_step_g7(const StepParams&, int, bool, bool, bool, int, int, int, hipStream_t);
-hipError_t launch_step_g8(const StepParams&, int, bool, bool, bool, int, int, int, hipStream_t);
-hipError_t launch_step_g9(const StepParams&, int, bool, bool, bool, int, int, int, hipStream_t);
-hipError_t launch_step_g10(const StepParams&, int, bool, bool, bool, int, int, int, hipStream_t);
-hipError_t launch_step_g11(const StepParams&, int, bool, bool, bool, int, int, int, hipStream_t);
-hipError_t launch_step_g12(const StepParams&, int, bool, bool, bool, int, int, int, hipStream_t);
-int blocks_step_g1(int, bool, bool, bool, int);
-int blocks_step_g2(int, bool, bool, bool, int);
-int blocks_step_g3(int, bool, bool, bool, int);
-int blocks_step_g4(int, bool, bool, bool, int);
-int blocks_step_g5(int, bool, bool, bool, int);
-int blocks_step_g6(int, bool, bool, bool, int);
-int blocks_step_g7(int, bool, bool, bool, int);
-int blocks_step_g8(int, bool, bool, bool, int);
-int blocks_step_g9(int, bool, bool, bool, int);
-int blocks_step_g10(int, bool, bool, bool, int);
-int blocks_step_g11(int, bool, bool, bool, int);
-int blocks_step_g12(int, bool, bool, bool, int);
+// dev::kernel_at_depth<G>, defined and instantiated only in depth G's object
+// (gol_step.hip): every other unit sees this declaration alone, so the
+// kernels of a depth live in that depth's code object.
+template <int G>
+StepKernel step_kernel_at(const StepInstance& k);
 
 }  // namespace gol
