@@ -145,10 +145,11 @@ void destroy_impl(gol_ctx* c) {
         if (ev) hip_note(hipEventDestroy(ev), "destroy: hipEventDestroy");
     for (void* p : {(void*)c->snap, (void*)c->clk_buf, (void*)c->plane[0], (void*)c->plane[1], (void*)c->halo_top,
                     (void*)c->halo_bot, (void*)c->zero_row, (void*)c->slots, (void*)c->region_stage,
-                    (void*)c->census_slots})
+                    (void*)c->census_slots, (void*)c->density_grid})
         if (p) hip_note(hipFree(p), "destroy: hipFree");
     if (c->host_folded) hip_note(hipHostFree(c->host_folded), "destroy: hipHostFree");
     if (c->census_host) hip_note(hipHostFree(c->census_host), "destroy: hipHostFree");
+    if (c->density_host) hip_note(hipHostFree(c->density_host), "destroy: hipHostFree");
     for (hipStream_t st : {c->compute, c->comm, c->edge, c->xfer})
         if (st) hip_note(hipStreamDestroy(st), "destroy: hipStreamDestroy");
     delete c;

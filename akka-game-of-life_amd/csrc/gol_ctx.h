@@ -10,8 +10,9 @@
 //   gol_group.cpp      in-process shard groups (gol_group_*)
 //   gol_checkpoint.cpp snapshots, checkpoints, restore and light-cone replay
 //   gol_profile.cpp    kernel timing, the in-kernel clock probe, gol_profile_*
-//   gol_region.cpp     census and windowed pattern I/O (gol_census,
-//                      gol_read_region, gol_write_region)
+//   gol_region.cpp     census, windowed pattern I/O and the density map
+//                      (gol_census, gol_read_region, gol_write_region,
+//                      gol_density)
 //
 // Reference correspondence (src/main/scala/gameoflife/ of the reference):
 //   gol_create   <- BoardCreator.createAllInitialActors (BoardCreator.scala:79-89)
@@ -106,6 +107,14 @@ struct gol_ctx {
     bool census_clean = false;                      // the slots hold the identity (left so by the fold)
     unsigned long long* census_host = nullptr;      // kCensusValues, page-locked, mapped
     unsigned long long* census_host_dev = nullptr;  // ... its device address
+    // density map (gol_density), allocated on first use and grown on demand:
+    // the device grid the kernels count into and the mapped page-locked words
+    // it is exported to before they are added into the caller's buffer
+    uint32_t* density_grid = nullptr;
+    uint32_t* density_host = nullptr;
+    uint32_t* density_host_dev = nullptr;  // ... its device address
+    size_t density_words = 0;
+    bool density_clean = false;            // the grid is all zero (left so by the export)
     // RCCL
     ncclComm_t nccl = nullptr;
     int rank = 0, nranks = 1;

@@ -205,4 +205,27 @@ hipError_t launch_region_scatter(uint32_t* dst, int64_t pitch, int32_t wwords, i
                                  int64_t x0, int64_t w, const uint32_t* stage, int mode, bool wrap_x,
                                  hipStream_t stream);
 
+// Density map (gol_density): the live cells of `nrows` device rows starting at
+// `src` -- window rows from `win_row` on -- per T x T tile, T = 1 << lg, tiles
+// anchored at the window origin.  `grid` is the rows' own part of the map: its
+// row 0 is tile row win_row >> lg, rows are `tw` counts apart and there are
+// `grid_rows` = the tile rows the window rows meet.  The two regimes meet at
+// T = 64: from there on a 64-column group meets at most two tiles, below it a
+// tile lies inside one 32-column window word.
+constexpr int kDensityCoarseLog2 = 6;
+// lg >= kDensityCoarseLog2.  Board columns [xa, xb) (no wrap; xa is window
+// column `koff`) are added to the grid with atomics: zero it first; pieces of
+// one window may share it.  16-byte loads, as launch_census.
+hipError_t launch_density_coarse(const uint32_t* src, int64_t pitch, int32_t wwords, int ilv, int32_t nrows,
+                                 int64_t win_row, int64_t xa, int64_t xb, int64_t koff, int lg, uint32_t* grid,
+                                 int64_t tw, int64_t grid_rows, hipStream_t stream);
+// lg < kDensityCoarseLog2.  Window columns [x0, x0 + w) (modulo the row, as
+// launch_region_gather); tw = ceil(w / T).  Every count of the grid is stored.
+hipError_t launch_density_fine(const uint32_t* src, int64_t pitch, int32_t wwords, int ilv, int32_t nrows,
+                               int64_t win_row, int64_t x0, int64_t w, int lg, uint32_t* grid, int64_t tw,
+                               int64_t grid_rows, hipStream_t stream);
+// out[0..n) = grid[0..n), which is left zero; `out` may be mapped host memory
+// (one launch in place of a copy and the next call's memset).
+hipError_t launch_density_export(uint32_t* grid, uint32_t* out, int64_t n, hipStream_t stream);
+
 }  // namespace gol

@@ -1,7 +1,8 @@
 // gol_region.cpp -- the board from the user's side without moving a plane:
 // gol_census (population and bounding box, one pass on the device),
 // gol_read_region and gol_write_region (a window of the torus or of the
-// clipped board, gathered from / scattered into the device layout).  They
+// clipped board, gathered from / scattered into the device layout) and
+// gol_density (the live cells per tile of a window: the zoomed-out view).  They
 // stand for what the reference offered at 7 x 7: the per-cell initialState of
 // BoardCreator.scala:65-70, the CellStateMsg stream a LoggerActor prints
 // (CellActor.scala:89, LoggerActor.scala:30-46) and the counting a reader of
@@ -35,10 +36,10 @@ int owned_runs(const gol_ctx* ctx, int64_t y0, int64_t h, RowRun runs[2]) {
     return n;
 }
 
-int check_window(gol_ctx* ctx, const char* what, int64_t x0, int64_t y0, int64_t w, int64_t h, const void* buf,
-                 int64_t host_pitch_words) {
+// The window rules every windowed call shares (include/gol.h "The window").
+int check_window(gol_ctx* ctx, const char* what, int64_t x0, int64_t y0, int64_t w, int64_t h, const void* buf) {
     if (!ctx) return set_err(nullptr, GOL_EINVAL, "%s: null context", what);
-    if (!buf) return set_err(ctx, GOL_EINVAL, "%s: null window buffer", what);
+    if (!buf) return set_err(ctx, GOL_EINVAL, "%s: null buffer", what);
     if (w < 1 || w > ctx->width || h < 1 || h > ctx->height || x0 < 0 || x0 >= ctx->width || y0 < 0 ||
         y0 >= ctx->height)
         return set_err(ctx, GOL_EINVAL, "%s: window %lld x %lld at (%lld, %lld) does not fit a %lld x %lld board", what,
@@ -48,6 +49,13 @@ int check_window(gol_ctx* ctx, const char* what, int64_t x0, int64_t y0, int64_t
         return set_err(ctx, GOL_EINVAL, "%s: window %lld x %lld at (%lld, %lld) leaves the clipped %lld x %lld board",
                        what, (long long)w, (long long)h, (long long)x0, (long long)y0, (long long)ctx->width,
                        (long long)ctx->height);
+    return GOL_OK;
+}
+
+// ... and a packed window buffer's pitch.
+int check_window(gol_ctx* ctx, const char* what, int64_t x0, int64_t y0, int64_t w, int64_t h, const void* buf,
+                 int64_t host_pitch_words) {
+    if (int rc = check_window(ctx, what, x0, y0, w, h, buf)) return rc;
     if (host_pitch_words < (w + 31) / 32)
         return set_err(ctx, GOL_EINVAL, "%s: host pitch %lld < %lld words per window row", what,
                        (long long)host_pitch_words, (long long)((w + 31) / 32));
@@ -69,6 +77,34 @@ int ensure_stage(gol_ctx* ctx, size_t words) {
                        words * sizeof(uint32_t));
     }
     ctx->region_stage_words = words;
+    return GOL_OK;
+}
+
+// The density grid and the mapped page-locked words it is exported to hold
+// `words` counts.  Nothing is in flight on them between calls: gol_density
+// synchronises before it adds.
+int ensure_density(gol_ctx* ctx, size_t words) {
+    if (words <= ctx->density_words) return GOL_OK;
+    uint32_t* old_grid = ctx->density_grid;
+    uint32_t* old_host = ctx->density_host;
+    ctx->density_grid = ctx->density_host = ctx->density_host_dev = nullptr;  // forgotten before they are freed
+    ctx->density_words = 0;
+    ctx->density_clean = false;
+    if (old_grid) HIP_CHECK(ctx, hipFree(old_grid));
+    if (old_host) HIP_CHECK(ctx, hipHostFree(old_host));
+    // coherent: the export's stores reach host memory without a cache flush
+    if (hipMalloc(&ctx->density_grid, words * sizeof(uint32_t)) != hipSuccess ||
+        hipHostMalloc((void**)&ctx->density_host, words * sizeof(uint32_t),
+                      hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess ||
+        hipHostGetDevicePointer((void**)&ctx->density_host_dev, ctx->density_host, 0) != hipSuccess) {
+        (void)hipGetLastError();
+        if (ctx->density_grid) hip_note(hipFree(ctx->density_grid), "gol_density: hipFree");
+        if (ctx->density_host) hip_note(hipHostFree(ctx->density_host), "gol_density: hipHostFree");
+        ctx->density_grid = ctx->density_host = ctx->density_host_dev = nullptr;
+        return set_err(ctx, GOL_ENOMEM, "allocating %zu bytes for the density map on the device and the host failed",
+                       words * sizeof(uint32_t));
+    }
+    ctx->density_words = words;
     return GOL_OK;
 }
 
@@ -169,6 +205,68 @@ int gol_write_region(gol_ctx* ctx, int64_t x0, int64_t y0, int64_t w, int64_t h,
         stage += r.count * sw;
     }
     HIP_CHECK(ctx, hipStreamSynchronize(ctx->compute));
+    return GOL_OK;
+}
+
+int gol_density(gol_ctx* ctx, int64_t x0, int64_t y0, int64_t w, int64_t h, int32_t log2_tile, uint32_t* counts,
+                int64_t pitch) {
+    if (int rc = check_window(ctx, "gol_density", x0, y0, w, h, counts)) return rc;
+    if (log2_tile < 0 || log2_tile > 15)
+        return set_err(ctx, GOL_EINVAL, "gol_density: log2_tile %d is not in 0 .. 15", log2_tile);
+    const int lg = log2_tile;
+    const int64_t tw = ((w - 1) >> lg) + 1;
+    if (pitch < tw)
+        return set_err(ctx, GOL_EINVAL, "gol_density: pitch %lld < %lld counts per map row", (long long)pitch,
+                       (long long)tw);
+    RowRun runs[2];
+    const int nruns = owned_runs(ctx, y0, h, runs);
+    if (nruns == 0) return GOL_OK;  // the window misses this shard
+    if (int rc = bind(ctx)) return rc;
+    // Each run counts into its own rows of the grid -- the tile rows its
+    // window rows meet -- so two runs (or two shards) that share a tile row
+    // each add their part of it to the caller's buffer.
+    int64_t map_row[2], map_rows[2];
+    size_t words = 0;
+    for (int k = 0; k < nruns; ++k) {
+        map_row[k] = runs[k].win_row >> lg;
+        map_rows[k] = ((runs[k].win_row + runs[k].count - 1) >> lg) - map_row[k] + 1;
+        words += (size_t)(map_rows[k] * tw);
+    }
+    if (int rc = ensure_density(ctx, words)) return rc;
+    // the window's columns as board columns that do not wrap: [xa, xb), xa being window column koff
+    const int64_t first = std::min(w, ctx->width - x0);
+    const int64_t piece[2][3] = {{x0, x0 + first, 0}, {0, w - first, first}};
+    // On the compute stream: after every queued pass and after the device
+    // copy of a snapshot in flight; the board, the epoch and the hash stay.
+    if (!ctx->density_clean)
+        HIP_CHECK(ctx, hipMemsetAsync(ctx->density_grid, 0, ctx->density_words * sizeof(uint32_t), ctx->compute));
+    ctx->density_clean = false;  // in use until the export has left it zero
+    uint32_t* grid = ctx->density_grid;
+    for (int k = 0; k < nruns; ++k) {
+        const RowRun& r = runs[k];
+        const uint32_t* src = ctx->plane[ctx->cur] + r.local_row * ctx->pitch;
+        if (lg >= gol::kDensityCoarseLog2) {
+            for (const auto& p : piece)
+                if (p[0] < p[1])
+                    HIP_CHECK(ctx, gol::launch_density_coarse(src, ctx->pitch, ctx->wwords, ctx->ilv, (int32_t)r.count,
+                                                              r.win_row, p[0], p[1], p[2], lg, grid, tw, map_rows[k],
+                                                              ctx->compute));
+        } else {
+            HIP_CHECK(ctx, gol::launch_density_fine(src, ctx->pitch, ctx->wwords, ctx->ilv, (int32_t)r.count, r.win_row,
+                                                    x0, w, lg, grid, tw, map_rows[k], ctx->compute));
+        }
+        grid += map_rows[k] * tw;
+    }
+    HIP_CHECK(ctx, gol::launch_density_export(ctx->density_grid, ctx->density_host_dev, (int64_t)words, ctx->compute));
+    HIP_CHECK(ctx, hipStreamSynchronize(ctx->compute));
+    ctx->density_clean = true;
+    const uint32_t* got = ctx->density_host;
+    for (int k = 0; k < nruns; ++k)
+        for (int64_t i = 0; i < map_rows[k]; ++i, got += tw) {
+            uint32_t* __restrict__ out = counts + (map_row[k] + i) * pitch;
+            const uint32_t* __restrict__ in = got;
+            for (int64_t j = 0; j < tw; ++j) out[j] += in[j];
+        }
     return GOL_OK;
 }
 

@@ -1,7 +1,8 @@
 // gol_region.hip -- the board seen from the user's side of the C ABI without
 // moving a plane: the census (population and bounding box in one pass over
-// the plane), and windows gathered from / scattered into the device layout
-// (gol_census, gol_read_region, gol_write_region in gol_region.cpp).
+// the plane), windows gathered from / scattered into the device layout, and
+// the density map of a window (gol_census, gol_read_region, gol_write_region,
+// gol_density in gol_region.cpp).
 #include <algorithm>
 
 #include "gol_kernels.h"
@@ -188,6 +189,13 @@ __device__ __forceinline__ uint32_t load_row_major(const uint32_t* row, int32_t 
     return row[c];
 }
 
+// 32 window columns of a device row: row-major words c0 and c1 (the next one,
+// modulo the row) funnel-shifted by sh = x0 % 32.
+__device__ __forceinline__ uint32_t window_word(const uint32_t* row, int32_t c0, int32_t c1, int sh, int ilv) {
+    const uint32_t lo = load_row_major(row, c0, ilv), hi = load_row_major(row, c1, ilv);
+    return (uint32_t)(((((unsigned long long)hi) << 32) | lo) >> sh);
+}
+
 // One thread per window word: word m of window row r holds window columns
 // 32 m .. 32 m + 31 = board columns from x0 + 32 m on, i.e. row-major words
 // c_first + m and the next one (modulo the row: torus widths are multiples
@@ -204,9 +212,7 @@ __global__ void region_gather_kernel(const uint32_t* __restrict__ src, int64_t p
         int32_t c0 = c_first + m;  // c_first < wwords, m < sw <= wwords
         if (c0 >= wwords) c0 -= wwords;
         const int32_t c1 = c0 + 1 == wwords ? 0 : c0 + 1;
-        const uint32_t* row = src + r * pitch;
-        const uint32_t lo = load_row_major(row, c0, ilv), hi = load_row_major(row, c1, ilv);
-        uint32_t v = (uint32_t)(((((unsigned long long)hi) << 32) | lo) >> sh);
+        uint32_t v = window_word(src + r * pitch, c0, c1, sh, ilv);
         if (m == sw - 1) v &= last_mask;
         stage[k] = v;
     }
@@ -289,6 +295,163 @@ __global__ void region_scatter_kernel(uint32_t* __restrict__ dst, int64_t pitch,
     }
 }
 
+// ---- density map ---------------------------------------------------------------
+// Live cells per T x T tile (T = 1 << lg) of a window, tiles anchored at the
+// window origin.  The host cuts the window into pieces that wrap neither way:
+// a run of owned rows (window row `wrow0` on) times board columns [xa, xb),
+// whose first column is window column `koff`.  `grid` is the run's part of the
+// map: row 0 is tile row wrow0 >> lg, `tw` counts per row, `grows` rows.
+
+// Bits [lo, hi) of a word, 0 <= lo, hi <= 32; empty when hi <= lo.
+__device__ __forceinline__ uint32_t bit_range(int lo, int hi) {
+    return hi > lo ? (uint32_t)(((1ull << hi) - 1ull) & ~((1ull << lo) - 1ull)) : 0u;
+}
+
+// Columns [lo, hi) (0 <= lo, hi <= 64) of a 64-column group as masks of its
+// two device words.  Pair layout: word j, bit b is column 2 b + j, so the
+// columns are bits ceil((lo - j) / 2) .. ceil((hi - j) / 2) - 1 of word j.
+template <int ILV>
+__device__ __forceinline__ void group_masks(int lo, int hi, uint32_t& m0, uint32_t& m1) {
+    if (ILV == 2) {
+        m0 = bit_range((lo + 1) >> 1, (hi + 1) >> 1);
+        m1 = bit_range(lo >> 1, hi >> 1);
+    } else {
+        m0 = bit_range(min(lo, 32), min(hi, 32));
+        m1 = bit_range(max(lo, 32) - 32, max(hi, 32) - 32);
+    }
+}
+
+constexpr int kDensityInFlight = 4;                       // 16-byte loads a lane issues before it counts
+constexpr int kDensityLdsTiles = 2 * kCensusThreads + 2;  // tiles a workgroup's columns can meet at T >= 64
+
+// Coarse tiles (T >= 64): the census's pass -- 16-byte loads, a workgroup of
+// 2^lgx chunks times 256 >> lgx rows -- with the lane's chunk fixed over a slab
+// of up to 2^lgr <= T window rows of one tile row.  A 64-column group meets at
+// most two tiles, so a lane holds two masks per word (all ones or zero away
+// from tile edges and the ends of the piece; columns outside [xa, xb), padding
+// words included, are in neither) and four counters.  The workgroup sums its
+// lanes per tile in LDS and adds what is not zero to the grid: one vector
+// atomic per tile, slab and workgroup.
+template <int ILV>
+__global__ __launch_bounds__(kCensusThreads) void density_coarse_kernel(const uint32_t* __restrict__ plane,
+                                                                        int64_t pitch, int32_t nrows, int64_t wrow0,
+                                                                        int64_t xa, int64_t xb, int64_t koff,
+                                                                        int32_t q_first, int32_t nchunks, int lgx,
+                                                                        int lg, int lgr, unsigned* grid, int64_t tw,
+                                                                        int64_t grows) {
+    __shared__ unsigned s_cnt[kDensityLdsTiles];
+    const int bx = 1 << lgx, by = kCensusThreads >> lgx;
+    const int tx = threadIdx.x & (bx - 1), ty = threadIdx.x >> lgx;
+    const int32_t xtiles = (nchunks + bx - 1) >> lgx;
+    const int64_t slab0 = wrow0 >> lgr;
+    const int64_t items = (((wrow0 + nrows - 1) >> lgr) - slab0 + 1) * xtiles;
+    const int span = 2 * bx + 2;
+    for (int t = threadIdx.x; t < span; t += kCensusThreads) s_cnt[t] = 0u;
+    __syncthreads();
+    for (int64_t it = blockIdx.x; it < items; it += gridDim.x) {
+        const int64_t sl = it / xtiles;
+        const int32_t xt = (int32_t)(it - sl * xtiles);
+        // the slab's rows: local rows [r_lo, r_hi) of the run, all of tile row `trow` of the grid
+        const int64_t wlo = max(wrow0, (slab0 + sl) << lgr), whi = min(wrow0 + nrows, (slab0 + sl + 1) << lgr);
+        const int32_t r_lo = (int32_t)(wlo - wrow0), r_hi = (int32_t)(whi - wrow0);
+        const int64_t trow = (wlo >> lg) - (wrow0 >> lg);
+        // the workgroup's first tile and the lane's chunk
+        const int32_t qb = q_first + xt * bx, q = qb + tx;
+        const int64_t tbase = (max(xa, 128 * (int64_t)qb) - xa + koff) >> lg;
+        const bool live = q < q_first + nchunks;
+        uint32_t m[2][2][2];  // [group][tile: first, next][word]
+        int lt[2];            // the group's first tile, relative to tbase
+#pragma unroll
+        for (int g = 0; g < 2; ++g) {
+            const int64_t g0 = 128 * (int64_t)q + 64 * g;
+            const int lo = (int)min(max(xa - g0, (int64_t)0), (int64_t)64);
+            const int hi = live ? (int)min(max(xb - g0, (int64_t)0), (int64_t)64) : 0;
+            const int64_t xc = min(max(g0, xa), xb - 1);  // the group's first column of the piece, or the nearest one
+            const int64_t t = (xc - xa + koff) >> lg;
+            // tile t + 1 begins at this column of the group
+            const int s = (int)min(max(((t + 1) << lg) - koff + xa - g0, (int64_t)lo), (int64_t)max(lo, hi));
+            group_masks<ILV>(lo, s, m[g][0][0], m[g][0][1]);
+            group_masks<ILV>(s, hi, m[g][1][0], m[g][1][1]);
+            lt[g] = (int)(t - tbase);
+        }
+        uint32_t cnt[2][2] = {{0u, 0u}, {0u, 0u}};
+        if (live) {
+            const uint32_t* col = plane + 4 * (int64_t)q;
+            for (int32_t r0 = r_lo + ty; r0 < r_hi; r0 += kDensityInFlight * by) {
+                uint4 v[kDensityInFlight];
+#pragma unroll
+                for (int u = 0; u < kDensityInFlight; ++u) {
+                    const int32_t r = r0 + u * by;
+                    v[u] = make_uint4(0u, 0u, 0u, 0u);
+                    if (r < r_hi) v[u] = *reinterpret_cast<const uint4*>(col + r * pitch);
+                }
+#pragma unroll
+                for (int u = 0; u < kDensityInFlight; ++u) {
+                    const uint32_t w[2][2] = {{v[u].x, v[u].y}, {v[u].z, v[u].w}};
+#pragma unroll
+                    for (int g = 0; g < 2; ++g)
+#pragma unroll
+                        for (int k = 0; k < 2; ++k)
+                            cnt[g][k] += (uint32_t)(__popc(w[g][0] & m[g][k][0]) + __popc(w[g][1] & m[g][k][1]));
+                }
+            }
+        }
+        // A count that is not zero belongs to a tile of the piece, which the two range checks below
+        // cannot refuse; they stay so that a slip in this arithmetic shows as a wrong count in the
+        // tests and never as a store outside the grid.
+#pragma unroll
+        for (int g = 0; g < 2; ++g)
+#pragma unroll
+            for (int k = 0; k < 2; ++k)
+                if (cnt[g][k] != 0u && (unsigned)(lt[g] + k) < (unsigned)span) atomicAdd(&s_cnt[lt[g] + k], cnt[g][k]);
+        __syncthreads();
+        for (int t = threadIdx.x; t < span; t += kCensusThreads) {
+            const unsigned c = s_cnt[t];
+            if (c == 0u) continue;
+            s_cnt[t] = 0u;  // left clean for the next item
+            if (tbase + t < tw && trow < grows) atomicAdd(grid + trow * tw + tbase + t, c);
+        }
+        __syncthreads();
+    }
+}
+
+// Fine tiles (T <= 32): one thread per tile of the run's part of the map.  A
+// tile lies inside one 32-column word of the window, gathered as
+// region_gather_kernel gathers it; the thread counts the tile's bits of that
+// word over the tile's rows and stores the count (every tile has one owner).
+__global__ void density_fine_kernel(const uint32_t* __restrict__ src, int64_t pitch, int32_t wwords, int ilv,
+                                    int32_t nrows, int64_t wrow0, int32_t c_first, int sh, int64_t w, int lg,
+                                    unsigned* __restrict__ grid, int64_t tw, int64_t grows) {
+    const int64_t total = grows * tw;
+    for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
+         idx += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t ti = idx / tw, k = idx - ti * tw;
+        const int64_t wtop = ((wrow0 >> lg) + ti) << lg;  // the tile's first window row
+        const int32_t r_lo = (int32_t)(max(wrow0, wtop) - wrow0);
+        const int32_t r_hi = (int32_t)(min(wrow0 + nrows, wtop + ((int64_t)1 << lg)) - wrow0);
+        const int64_t c = k << lg;  // the tile's first window column
+        const int o = (int)(c & 31);
+        const uint32_t mask = bit_range(o, o + (int)min((int64_t)1 << lg, w - c));
+        int32_t c0 = c_first + (int32_t)(c >> 5);  // c_first < wwords, c / 32 < ceil(w / 32) <= wwords
+        if (c0 >= wwords) c0 -= wwords;
+        const int32_t c1 = c0 + 1 == wwords ? 0 : c0 + 1;
+        unsigned count = 0u;
+        for (int32_t r = r_lo; r < r_hi; ++r) count += (unsigned)__popc(window_word(src + r * pitch, c0, c1, sh, ilv) & mask);
+        grid[idx] = count;
+    }
+}
+
+// The grid's first n counts to `out` -- mapped page-locked host memory, read
+// after the stream synchronises -- leaving the grid zero for the next call.
+__global__ void density_export_kernel(unsigned* __restrict__ grid, unsigned* __restrict__ out, int64_t n) {
+    for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < n;
+         idx += (int64_t)gridDim.x * blockDim.x) {
+        const unsigned c = grid[idx];
+        out[idx] = c;
+        if (c != 0u) grid[idx] = 0u;
+    }
+}
+
 int grid_for(int64_t total) { return (int)std::max<int64_t>(1, std::min<int64_t>((total + 255) / 256, 2048)); }
 
 uint32_t last_word_mask(int64_t w) { return w % 32 ? (uint32_t)((1ull << (w % 32)) - 1ull) : 0xFFFFFFFFu; }
@@ -345,6 +508,49 @@ hipError_t launch_region_scatter(uint32_t* dst, int64_t pitch, int32_t wwords, i
     return launch_kernel(region_scatter_kernel, dim3(grid_for((int64_t)nrows * nunits)), dim3(256), stream, dst, pitch,
                          units, ilv, nrows, (int32_t)(x0 / span), nunits, x0, width, wrap_x ? 1 : 0, stage, sw,
                          last_word_mask(w), mode);
+}
+
+hipError_t launch_density_coarse(const uint32_t* src, int64_t pitch, int32_t wwords, int ilv, int32_t nrows,
+                                 int64_t win_row, int64_t xa, int64_t xb, int64_t koff, int lg, uint32_t* grid,
+                                 int64_t tw, int64_t grid_rows, hipStream_t stream) {
+    // 16-byte loads, as the census: aligned rows that hold whole chunks
+    if ((ilv != 1 && ilv != 2) || pitch % 4 != 0 || pitch < (wwords + 3) / 4 * 4 || nrows < 1 || win_row < 0 ||
+        xa < 0 || xa >= xb || xb > 32 * (int64_t)wwords || koff < 0 || lg < kDensityCoarseLog2 || lg > 15 || tw < 1 ||
+        grid_rows != ((win_row + nrows - 1) >> lg) - (win_row >> lg) + 1 || ((koff + xb - xa - 1) >> lg) >= tw ||
+        (reinterpret_cast<uintptr_t>(src) & 15) != 0)
+        return hipErrorInvalidValue;
+    const int32_t q_first = (int32_t)(xa / 128), nchunks = (int32_t)((xb + 127) / 128) - q_first;
+    int lgx = 0;
+    while (lgx < 8 && (1 << lgx) < nchunks) ++lgx;
+    // a slab: up to 64 rows per lane, within one tile row
+    const int lgr = std::min(lg, 8 - lgx + 6);
+    const int64_t slabs = ((win_row + nrows - 1) >> lgr) - (win_row >> lgr) + 1;
+    const int64_t items = slabs * ((nchunks + (1 << lgx) - 1) >> lgx);
+    const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>(items, 2048));  // as the census
+    unsigned* g = reinterpret_cast<unsigned*>(grid);
+    if (ilv == 2)
+        return launch_kernel(density_coarse_kernel<2>, dim3(blocks), dim3(kCensusThreads), stream, src, pitch, nrows,
+                             win_row, xa, xb, koff, q_first, nchunks, lgx, lg, lgr, g, tw, grid_rows);
+    return launch_kernel(density_coarse_kernel<1>, dim3(blocks), dim3(kCensusThreads), stream, src, pitch, nrows,
+                         win_row, xa, xb, koff, q_first, nchunks, lgx, lg, lgr, g, tw, grid_rows);
+}
+
+hipError_t launch_density_fine(const uint32_t* src, int64_t pitch, int32_t wwords, int ilv, int32_t nrows,
+                               int64_t win_row, int64_t x0, int64_t w, int lg, uint32_t* grid, int64_t tw,
+                               int64_t grid_rows, hipStream_t stream) {
+    if ((ilv != 1 && ilv != 2) || nrows < 1 || win_row < 0 || w < 1 || w > 32 * (int64_t)wwords || x0 < 0 ||
+        x0 >= 32 * (int64_t)wwords || lg < 0 || lg >= kDensityCoarseLog2 || tw != ((w - 1) >> lg) + 1 ||
+        grid_rows != ((win_row + nrows - 1) >> lg) - (win_row >> lg) + 1)
+        return hipErrorInvalidValue;
+    return launch_kernel(density_fine_kernel, dim3(grid_for(grid_rows * tw)), dim3(256), stream, src, pitch, wwords,
+                         ilv, nrows, win_row, (int32_t)(x0 / 32), (int)(x0 % 32), w, lg,
+                         reinterpret_cast<unsigned*>(grid), tw, grid_rows);
+}
+
+hipError_t launch_density_export(uint32_t* grid, uint32_t* out, int64_t n, hipStream_t stream) {
+    if (n < 1) return hipErrorInvalidValue;
+    return launch_kernel(density_export_kernel, dim3(grid_for(n)), dim3(256), stream,
+                         reinterpret_cast<unsigned*>(grid), reinterpret_cast<unsigned*>(out), n);
 }
 
 }  // namespace gol

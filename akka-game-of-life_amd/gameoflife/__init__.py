@@ -8,7 +8,8 @@ Mirrors the reference package ``gameoflife`` (src/main/scala/gameoflife/):
                  that replaces CellActor + NextStateCellGathererActor);
 * ``shard``   -- row-block decomposition and the multi-rank driver;
 * ``rules``   -- Life-like (birth, survive) masks incl. the reference's rules;
-* ``patterns`` -- RLE and O/. patterns as cell arrays for ``GolEngine.place``.
+* ``patterns`` -- RLE and O/. patterns as cell arrays for ``GolEngine.place``;
+* ``view``    -- a density map (``GolEngine.density``) as text or a PGM image.
 
 ``engine`` (and everything that computes) needs ``lib/libgol.so``; it raises
 on import when the library is missing -- there is no CPU fallback.

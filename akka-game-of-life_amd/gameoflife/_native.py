@@ -166,6 +166,7 @@ _SIGNATURES = {
     "gol_read_region": (_c.c_int, [_vp, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_int64, _u32p, _c.c_int64]),
     "gol_write_region": (_c.c_int, [_vp, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_int64, _u32p, _c.c_int64,
                                     _c.c_int32]),
+    "gol_density": (_c.c_int, [_vp, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_int32, _u32p, _c.c_int64]),
 }
 
 

@@ -191,6 +191,23 @@ class GolEngine:
         (gameoflife.patterns) -- with its top-left cell at (x, y)."""
         self.write_region(x, y, patterns.as_cells(pattern), mode)
 
+    def _density_into(self, x: int, y: int, w: int, h: int, log2_tile: int, counts: np.ndarray) -> None:
+        self._chk(N.lib.gol_density(self._h, x, y, w, h, log2_tile, counts.ctypes.data_as(N._u32p), counts.shape[1]))
+
+    def density(self, tile: int, x: int = 0, y: int = 0, w: int | None = None, h: int | None = None) -> np.ndarray:
+        """The zoomed-out view, counted on the device: a uint32 [th][tw] map
+        of the live cells per tile x tile block of the w x h window at (x, y),
+        tiles anchored at the window origin, the last one in each direction
+        possibly partial.  `tile` is a power of two from 1 to 32768; w and h
+        default to the rest of the board from (x, y) -- on a torus, which
+        wraps the window, to the whole width and height.  Rows this shard
+        does not own count nothing (ShardGroup.density sums the shards)."""
+        lg = _log2_tile(tile)
+        w, h = _density_window(self, x, y, w, h)
+        counts = _density_buffer(w, h, lg)
+        self._density_into(x, y, w, h, lg, counts)
+        return counts
+
     def checkpoint(self) -> np.ndarray:
         """gol_checkpoint into a new uint8 array (a bytes-like buffer: file
         writes, parse_checkpoint and restore take it as is).  No zero-fill and
@@ -371,6 +388,16 @@ class ShardGroup:
     def place(self, pattern, x: int, y: int, mode: str = "or") -> None:
         self.write_region(x, y, patterns.as_cells(pattern), mode)
 
+    def density(self, tile: int, x: int = 0, y: int = 0, w: int | None = None, h: int | None = None) -> np.ndarray:
+        """The board's density map (GolEngine.density): every shard adds the
+        cells of its own rows to one zeroed buffer."""
+        lg = _log2_tile(tile)
+        w, h = _density_window(self.shards[0], x, y, w, h)
+        counts = _density_buffer(w, h, lg)
+        for s in self.shards:
+            s._density_into(x, y, w, h, lg, counts)
+        return counts
+
     def hash(self) -> int:
         """The board's state hash: the shards' partials summed mod 2^64."""
         return sum(s.hash() for s in self.shards) & 0xFFFFFFFFFFFFFFFF
@@ -402,6 +429,26 @@ def _window_buffer(w: int, h: int) -> np.ndarray:
     """A zeroed packed buffer for a w x h window (gol_read_region fills the
     rows a shard owns and leaves the others as they are)."""
     return np.zeros((max(int(h), 1), max(codec.words_per_row(int(w)), 1)), dtype=np.uint32)
+
+
+def _log2_tile(tile: int) -> int:
+    """log2 of a density tile edge; ValueError unless it is a power of two
+    from 1 to 32768 (gol_density's log2_tile 0 .. 15)."""
+    if not isinstance(tile, (int, np.integer)) or isinstance(tile, bool) or not 1 <= tile <= 32768 or tile & (tile - 1):
+        raise ValueError(f"tile must be a power of two from 1 to 32768, not {tile!r}")
+    return int(tile).bit_length() - 1
+
+
+def _density_window(e: GolEngine, x: int, y: int, w: int | None, h: int | None) -> tuple[int, int]:
+    torus = e.topology == "torus"
+    return (int((e.width if torus else e.width - x) if w is None else w),
+            int((e.height if torus else e.height - y) if h is None else h))
+
+
+def _density_buffer(w: int, h: int, log2_tile: int) -> np.ndarray:
+    """A zeroed [th][tw] map for a w x h window (gol_density adds to it)."""
+    t = 1 << log2_tile
+    return np.zeros((max(-(-h // t), 1), max(-(-w // t), 1)), dtype=np.uint32)
 
 
 class _HostBlock:

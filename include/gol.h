@@ -52,8 +52,8 @@ extern "C" {
  * header comment); the values of tori with an even word count are unchanged,
  * those of row-major boards (clipped, odd word counts) differ from version 1.
  * The entry points and structs are those of version 1.  gol_census,
- * gol_read_region and gol_write_region were added without a new version:
- * additive entry points change nothing a version-2 caller relies on. */
+ * gol_read_region, gol_write_region and gol_density were added without a new
+ * version: additive entry points change nothing a version-2 caller relies on. */
 #define GOL_ABI_VERSION 2
 
 /* Return codes. */
@@ -291,6 +291,43 @@ int gol_read_region(gol_ctx* ctx, int64_t x0, int64_t y0, int64_t w, int64_t h,
                     uint32_t* packed_out, int64_t host_pitch_words);
 int gol_write_region(gol_ctx* ctx, int64_t x0, int64_t y0, int64_t w, int64_t h,
                      const uint32_t* packed, int64_t host_pitch_words, int32_t mode);
+
+/* Density map: the zoomed-out view of a window, counted on the device.  Each
+ * entry is the number of live cells in a T x T tile, T = 1 << log2_tile,
+ * 0 <= log2_tile <= 15 (a full tile holds at most 2^30 cells).  Replaces the
+ * LoggerActor printing the board (LoggerActor.scala:30-46) at a scale where a
+ * board can no longer be printed -- or shipped -- cell by cell: one pass over
+ * the window's words on the device, and only the map crosses the bus.
+ *
+ * The window follows the rules of gol_read_region above (a torus wraps, a
+ * GOL_REF_CLIPPED window lies inside the stored board, whose cells outside
+ * the visible extent count as they do in gol_census).  Tiles are anchored at
+ * the window origin, not at board coordinate 0: tile (k, i) covers window
+ * columns k T .. min(w, (k + 1) T) - 1 and window rows i T ..
+ * min(h, (i + 1) T) - 1, so the map has th = ceil(h / T) rows of
+ * tw = ceil(w / T) counts and the last tile in each direction may be partial.
+ * `pitch` is in counts, pitch >= tw.
+ *
+ * The call ADDS to counts[i * pitch + k] the live cells of tile (k, i) that
+ * lie in the shard's rows [row0, row0 + rows); the caller zeroes the buffer
+ * first.  Entries past tw of a map row are not touched, nor are map rows none
+ * of whose board rows belong to the shard; a window that misses the shard
+ * returns GOL_OK with the buffer unchanged.  A sharded caller therefore
+ * issues the same call with the same zeroed buffer on every shard -- of an
+ * in-process group, a loopback ring or an RCCL ring, whether or not shard
+ * boundaries cut through tile rows -- and gets the whole map: the windows'
+ * convention with a sum in place of a fill.
+ *
+ * A null context or buffer, log2_tile outside 0 .. 15, pitch < tw and a
+ * window out of range return GOL_EINVAL with a message before any device
+ * work is queued, and leave the buffer untouched.  The call is ordered on the
+ * compute stream after every queued pass and after the device copy of a
+ * snapshot in flight, and synchronises before it returns; it changes neither
+ * the board, the epoch nor the hash, and is valid with a communicator or a
+ * group attached.  The device grid it counts into belongs to the context and
+ * grows on demand (GOL_ENOMEM if a map does not fit: 32 bits per tile). */
+int gol_density(gol_ctx* ctx, int64_t x0, int64_t y0, int64_t w, int64_t h, int32_t log2_tile,
+                uint32_t* counts, int64_t pitch);
 
 /* Shard checkpoint = {header with epoch + geometry, packed board}.  Replaces
  * the reference's recovery state (initialState kept by the frontend,
