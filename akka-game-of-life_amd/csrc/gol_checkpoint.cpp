@@ -93,11 +93,17 @@ int gol_replay(gol_ctx* ctx, uint32_t generations, const uint32_t* above, const 
     // dead (their garbage moves one row per generation and never reaches the
     // shard's rows).  Each generation's partial hash covers the shard's rows.
     const PlaneGeom geom{(int32_t)ext, ctx->row0 - n};
-    const int32_t lo[1] = {0}, hi[1] = {(int32_t)ext};
+    PassLaunch L;
+    L.halo_top = L.halo_bot = ctx->zero_row;
+    L.hi[0] = (int32_t)ext;
+    L.prof_kind = kProfNone;
+    L.stream = ctx->compute;
+    L.geom = &geom;
     int cur = 0;
     for (int64_t g = 0; g < n; ++g) {
-        if (int rc = launch_ranges(ctx, 1, blk[cur], blk[cur ^ 1], ctx->zero_row, ctx->zero_row, 0, false, nullptr, 1,
-                                   lo, hi, kProfNone, ctx->compute, &geom)) {
+        L.cur = blk[cur];
+        L.nxt = blk[cur ^ 1];
+        if (int rc = launch_ranges(ctx, L)) {
             release();
             return rc;
         }

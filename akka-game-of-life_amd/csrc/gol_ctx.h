@@ -3,8 +3,13 @@
 //
 //   gol_capi.cpp       error state, context lifetime, seeding, stepping, hashes,
 //                      tuning and the remaining small entry points
-//   gol_schedule.cpp   pass planner, band / tail / XCD tuning, kernel launches
-//                      of a pass (whole shard, interior and boundary rows)
+//   gol_plan.h         the schedule rules as pure functions of integers (no HIP,
+//                      no context): band plan of a launch (band height,
+//                      small-board cut, tail split, grid), XCD chunk, depth
+//                      planner -- checked on the CPU (tests/schedule_probe.cpp)
+//   gol_schedule.cpp   kernel instance and strip count of a pass, its kernel
+//                      launches (whole shard, interior and boundary rows) and
+//                      pass plan: gathers gol_plan.h's inputs from the context
 //   gol_ring.cpp       the ring schedule: RCCL and loopback halo exchange,
 //                      one_pass, gol_comm_*
 //   gol_group.cpp      in-process shard groups (gol_group_*)
@@ -222,10 +227,29 @@ struct PlaneGeom {
     int64_t grow0;
 };
 
-int launch_ranges(gol_ctx* ctx, int gens, const uint32_t* cur, uint32_t* nxt, const uint32_t* htop,
-                  const uint32_t* hbot, int64_t halo_stride, bool wrap_y, unsigned long long* slots, int n,
-                  const int32_t* lo, const int32_t* hi, int prof_kind, hipStream_t stream = nullptr,
-                  const PlaneGeom* geom = nullptr);
+// One launch of a pass: `gens` generations over local row ranges
+// [lo[0], hi[0]) (+ [lo[1], hi[1]) if n == 2).
+struct PassLaunch {
+    int gens = 1;
+    const uint32_t* cur = nullptr;       // local row 0 of the current plane
+    uint32_t* nxt = nullptr;             // ... of the next plane
+    const uint32_t* halo_top = nullptr;  // rows -gens .. -1 and rows .. rows + gens - 1, halo_stride words apart
+    const uint32_t* halo_bot = nullptr;  // (0: one row repeated)
+    int64_t halo_stride = 0;
+    bool wrap_y = false;                 // unsharded torus: rows wrap inside the plane, no halo read
+    unsigned long long* slots = nullptr;  // hash accumulators of these generations, or null (unhashed)
+    int n = 1;
+    int32_t lo[2] = {0, 0}, hi[2] = {0, 0};
+    int prof_kind = kProfMain;
+    hipStream_t stream = nullptr;    // null: the compute stream
+    const PlaneGeom* geom = nullptr;  // null: the context's own plane
+};
+
+// Column strips of a row for instance `k`; `halo_lanes`: as if the pass ran
+// halo-lane strips even where it runs whole-row waves (the planner's
+// small-board test).
+int strip_count(const gol_ctx* ctx, gol::StepInstance k, bool halo_lanes = false);
+int launch_ranges(gol_ctx* ctx, const PassLaunch& launch);
 int sharded_interior(gol_ctx* ctx, int G, unsigned long long* slots, bool has_up, bool has_down);
 int sharded_boundary(gol_ctx* ctx, int G, unsigned long long* slots, bool has_up, bool has_down,
                      const hipEvent_t* halo_ready, int nready);

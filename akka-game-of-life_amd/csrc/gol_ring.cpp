@@ -264,9 +264,15 @@ int one_pass(gol_ctx* ctx, int G, unsigned long long* slots) {
     const int64_t pitch = ctx->pitch;
     if (!sharded(ctx)) {
         // torus: rows wrap inside the plane; clipped: outside rows are dead
-        const int32_t lo[1] = {0}, hi[1] = {rows};
-        int rc = launch_ranges(ctx, G, cur, nxt, ctx->zero_row, ctx->zero_row, 0, torus, slots, 1, lo, hi, kProfMain);
-        if (rc) return rc;
+        PassLaunch L;
+        L.gens = G;
+        L.cur = cur;
+        L.nxt = nxt;
+        L.halo_top = L.halo_bot = ctx->zero_row;
+        L.wrap_y = torus;
+        L.slots = slots;
+        L.hi[0] = rows;
+        if (int rc = launch_ranges(ctx, L)) return rc;
     } else if (ctx->group) {
         return set_err(ctx, GOL_ESTATE, "context belongs to a shard group: step it with gol_group_step");
     } else {

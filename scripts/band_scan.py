@@ -4,7 +4,7 @@ rounds, scored by kernel GCUPS per probed GHz (the held clock varies by box
 and over a run; the per-GHz rate does not).
 
     python scripts/band_scan.py [EDGE|WxH] [G] [GENS] [TAILS] [h]
-GOL_TAIL="frac,div" forces the tail split (gol_schedule.cpp tail_split);
+GOL_TAIL="frac,div" forces the tail split (gol_plan.h tail_split);
 TAILS ("f,d;B@f,d;B@-;...") scans only those, at the automatic band or at
 band B (with that tail, or none); "h" times the
 hashed passes.

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Pass depth on small tori under the small-board band rule (band_rows
-automatic, gol_schedule.cpp small_board_band): for every fixed depth G, the
+automatic, gol_plan.h small_board_band): for every fixed depth G, the
 wall and kernel microseconds per generation of N generations (default 1000,
 configs[1]), unhashed and hashed, min of 3 runs; then the library's own plan.
 

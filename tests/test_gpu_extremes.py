@@ -8,7 +8,7 @@ oracle (bit-exact boards and every generation's hash).
   whose halo lanes wrap onto the same pair), and of one word (32 columns,
   row-major);
 * a clipped board of 2^20 + 5 columns (a partial last word) and 40 rows;
-* the small-board band rule's smallest bands (gol_schedule.cpp
+* the small-board band rule's smallest bands (gol_plan.h
   small_board_band) on tori of 1 and 2 strips, at every depth the planner
   picks and a few fixed ones;
 * whole-row waves (gol_kernels.h whole_row_fits: a 4096-column B3/S23 torus
@@ -16,7 +16,7 @@ oracle (bit-exact boards and every generation's hash).
   rotates): square and odd-height boards, fixed bands from 1 row to more than
   the board, hashed and not, and as a 1-rank RCCL self-ring (interior and
   boundary launches);
-* the tail split (gol_schedule.cpp tail_split: the last round of resident
+* the tail split (gol_plan.h tail_split: the last round of resident
   waves in bands of band / 6 below 768-row bands) on boards of an odd row
   count, so the bulk range ends in a partial band before the tail bands.
 The planner chooses the depths unless a test fixes them."""
