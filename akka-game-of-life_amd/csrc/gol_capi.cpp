@@ -145,11 +145,12 @@ void destroy_impl(gol_ctx* c) {
         if (ev) hip_note(hipEventDestroy(ev), "destroy: hipEventDestroy");
     for (void* p : {(void*)c->snap, (void*)c->clk_buf, (void*)c->plane[0], (void*)c->plane[1], (void*)c->halo_top,
                     (void*)c->halo_bot, (void*)c->zero_row, (void*)c->slots, (void*)c->region_stage,
-                    (void*)c->census_slots, (void*)c->density_grid})
+                    (void*)c->census_slots, (void*)c->density_grid, (void*)c->active_bits})
         if (p) hip_note(hipFree(p), "destroy: hipFree");
     if (c->host_folded) hip_note(hipHostFree(c->host_folded), "destroy: hipHostFree");
     if (c->census_host) hip_note(hipHostFree(c->census_host), "destroy: hipHostFree");
     if (c->density_host) hip_note(hipHostFree(c->density_host), "destroy: hipHostFree");
+    if (c->active_host) hip_note(hipHostFree(c->active_host), "destroy: hipHostFree");
     for (hipStream_t st : {c->compute, c->comm, c->edge, c->xfer})
         if (st) hip_note(hipStreamDestroy(st), "destroy: hipStreamDestroy");
     delete c;
@@ -343,6 +344,7 @@ int gol_seed(gol_ctx* ctx, uint64_t seed) {
     if (int rc = bind(ctx)) return rc;
     HIP_CHECK(ctx, gol::launch_seed(ctx->plane[ctx->cur], ctx->pitch, ctx->wwords, ctx->width, ctx->row0,
                                     (int32_t)ctx->rows, seed, ctx->ilv, ctx->compute));
+    live_unknown(ctx, ctx->cur);
     ctx->epoch = 0;
     HIP_CHECK(ctx, hipStreamSynchronize(ctx->compute));
     return GOL_OK;
@@ -363,6 +365,8 @@ int gol_load(gol_ctx* ctx, const uint32_t* packed, int64_t host_pitch_words) {
     if (int rc = bind(ctx)) return rc;
     // interleaved layouts: upload into the spare plane, interleave into the current one
     uint32_t* dst = ctx->ilv > 1 ? ctx->plane[ctx->cur ^ 1] : ctx->plane[ctx->cur];
+    live_unknown(ctx, ctx->cur);
+    if (ctx->ilv > 1) live_unknown(ctx, ctx->cur ^ 1);
     HIP_CHECK(ctx, hipMemcpy2DAsync(dst, ctx->pitch * 4, packed, host_pitch_words * 4, (size_t)ctx->wwords * 4,
                                     ctx->rows, hipMemcpyHostToDevice, ctx->compute));
     if (ctx->ilv > 1)

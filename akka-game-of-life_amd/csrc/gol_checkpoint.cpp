@@ -114,6 +114,7 @@ int gol_replay(gol_ctx* ctx, uint32_t generations, const uint32_t* above, const 
             if (e != hipSuccess) return fail_hip(e, "light-cone hash");
         }
     }
+    live_unknown(ctx, ctx->cur);
     e = hipMemcpyAsync(ctx->plane[ctx->cur], blk[cur] + n * pitch, (size_t)ctx->rows * pitch * 4,
                        hipMemcpyDeviceToDevice, ctx->compute);
     if (e != hipSuccess) return fail_hip(e, "light-cone result");
@@ -138,6 +139,7 @@ int gol_snapshot(gol_ctx* ctx, uint32_t* packed_out, int64_t host_pitch_words) {
     // passes: the compute stream is ordered after every reader of the last pass)
     const uint32_t* src = ctx->plane[ctx->cur];
     if (ctx->ilv > 1) {
+        live_unknown(ctx, ctx->cur ^ 1);  // the spare plane holds row-major rows from here on
         HIP_CHECK(ctx, gol::launch_convert(src, ctx->plane[ctx->cur ^ 1], ctx->pitch, ctx->wwords,
                                            (int32_t)ctx->rows, false, ctx->ilv, ctx->compute));
         src = ctx->plane[ctx->cur ^ 1];

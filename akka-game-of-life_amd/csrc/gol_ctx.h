@@ -7,11 +7,16 @@
 //                      no context): band plan of a launch (band height,
 //                      small-board cut, tail split, grid), XCD chunk, depth
 //                      planner -- checked on the CPU (tests/schedule_probe.cpp)
+//   gol_active.h       active-row stepping as pure functions (no HIP, no
+//                      context): row runs that can hold a live cell, their
+//                      growth per pass, what to clear, when to scan -- checked
+//                      on the CPU (tests/active_probe.cpp)
 //   gol_schedule.cpp   kernel instance and strip count of a pass, its kernel
 //                      launches (whole shard, interior and boundary rows) and
 //                      pass plan: gathers gol_plan.h's inputs from the context
 //   gol_ring.cpp       the ring schedule: RCCL and loopback halo exchange,
-//                      one_pass, gol_comm_*
+//                      one_pass (and its active-row branch, gol_set_active_rows,
+//                      gol_active_*), gol_comm_*
 //   gol_group.cpp      in-process shard groups (gol_group_*)
 //   gol_checkpoint.cpp snapshots, checkpoints, restore and light-cone replay
 //   gol_profile.cpp    kernel timing, the in-kernel clock probe, gol_profile_*
@@ -38,6 +43,7 @@
 #include <vector>
 
 #include "../../include/gol.h"
+#include "gol_active.h"
 #include "gol_kernels.h"
 
 struct LoopRing;  // gol_ring.cpp
@@ -65,6 +71,13 @@ struct EventPair {
 
 // Clock-probe slots per context (one per profiled launch between folds).
 constexpr uint32_t kClockSlots = 1024;  // 4 KiB each
+
+// The rows of a plane that can hold a live cell: every
+// word of the plane outside `runs` (local rows) is zero, or nothing is known.
+struct LiveRows {
+    bool known = true;  // false: any row may be non-zero (`runs` is empty then)
+    golactive::Runs runs;
+};
 
 }  // namespace golc
 #pragma GCC visibility pop
@@ -120,6 +133,18 @@ struct gol_ctx {
     uint32_t* density_host_dev = nullptr;  // ... its device address
     size_t density_words = 0;
     bool density_clean = false;            // the grid is all zero (left so by the export)
+    // active-row stepping (gol_active.h, gol_ring.cpp):
+    // live[p] is kept for plane p by every writer of a plane, mode on or off
+    golc::LiveRows live[2];                // gol_create clears both planes: known, no runs
+    bool active_on = false;                // gol_set_active_rows
+    int64_t active_scan_rows = 0;          // rows of the current plane's runs after the last scan
+    int active_backoff = 0;                // passes between scans while they keep finding the board dense
+    int active_wait = 0;                   // ... of them still to go before the next scan
+    gol_active_stats active_stats{};
+    uint32_t* active_bits = nullptr;       // the scan's block bitmap (device), one bit per kActiveBlock rows
+    uint32_t* active_host = nullptr;       // ... exported here: page-locked, mapped
+    uint32_t* active_host_dev = nullptr;   // ... its device address
+    bool active_bits_clean = false;        // the device bitmap is all zero (left so by the export)
     // RCCL
     ncclComm_t nccl = nullptr;
     int rank = 0, nranks = 1;
@@ -271,6 +296,17 @@ struct HaloOp {
 
 int one_pass(gol_ctx* ctx, int G, unsigned long long* slots);
 void loop_leave(gol_ctx* ctx);
+
+// What the writers of a plane owe the active-row invariant (LiveRows):
+// plane p may now hold anything ...
+inline void live_unknown(gol_ctx* ctx, int p) { ctx->live[p] = LiveRows{false, {}}; }
+// ... or may have gained live cells in local rows [lo, hi) only.
+inline void live_add(gol_ctx* ctx, int p, int64_t lo, int64_t hi) {
+    LiveRows& l = ctx->live[p];
+    if (!l.known) return;
+    l.runs.push_back({(int32_t)lo, (int32_t)hi});
+    l.runs = golactive::normalize(std::move(l.runs), (int32_t)ctx->rows);
+}
 
 // ---- shard groups (gol_group.cpp) ------------------------------------------
 

@@ -72,6 +72,8 @@ int group_pass(gol_group* g, int G, const std::vector<unsigned long long*>& slot
             return group_fail(g, s, rc);
     }
     for (gol_ctx* s : g->shards) {
+        live_unknown(s, 0);  // stepped dense: active-row stepping covers contexts stepped whole only
+        live_unknown(s, 1);
         s->cur ^= 1;
         s->epoch += (uint64_t)G;
     }

@@ -56,7 +56,10 @@ int fold_profile(gol_ctx* ctx) {
         if (kind == kProfExchange) {
             ctx->prof_xchg_ms += ms;
             ctx->prof_xchg += 1;
-            ctx->prof_xchg_exposed_ms += after;
+            // the part of the exchange the interior did not hide: never more than the exchange itself.  On
+            // a short shard the interior launch can end before the exchange's first event fires on the
+            // comm stream; the time between the two belongs to neither.
+            ctx->prof_xchg_exposed_ms += std::min(after, ms);
             continue;
         }
         if (kind == kProfBoundary) {

@@ -202,6 +202,7 @@ int gol_write_region(gol_ctx* ctx, int64_t x0, int64_t y0, int64_t w, int64_t h,
         HIP_CHECK(ctx, gol::launch_region_scatter(ctx->plane[ctx->cur] + r.local_row * ctx->pitch, ctx->pitch,
                                                   ctx->wwords, ctx->width, ctx->ilv, (int32_t)r.count, x0, w, stage,
                                                   mode, ctx->topology == GOL_TORUS, ctx->compute));
+        live_add(ctx, ctx->cur, r.local_row, r.local_row + r.count);  // no scan: place() then step() stays O(pattern)
         stage += r.count * sw;
     }
     HIP_CHECK(ctx, hipStreamSynchronize(ctx->compute));

@@ -2,7 +2,8 @@
 // moving a plane: the census (population and bounding box in one pass over
 // the plane), windows gathered from / scattered into the device layout, and
 // the density map of a window (gol_census, gol_read_region, gol_write_region,
-// gol_density in gol_region.cpp).
+// gol_density in gol_region.cpp), and the row-occupancy scan of active-row
+// stepping (gol_ring.cpp).
 #include <algorithm>
 
 #include "gol_kernels.h"
@@ -452,6 +453,71 @@ __global__ void density_export_kernel(unsigned* __restrict__ grid, unsigned* __r
     }
 }
 
+// ---- row occupancy ---------------------------------------------------------------
+// Which blocks of kOccupancyBlock rows hold a non-zero word (active-row
+// stepping, gol_ring.cpp): bit b of `bits` is set iff block b of the plane
+// does, for the blocks of local rows [lo, hi), lo a multiple of the block.
+// The census's pass -- 16-byte loads, kOccInFlight on their way, a workgroup
+// of 2^lgx chunks times 256 >> lgx rows -- with an OR in place of the counts.
+// The layout does not matter (a non-zero word is a live word in either), nor
+// do the words of the pitch padding, which are zero.  A workgroup takes `per`
+// consecutive tiles, row tile by row tile, so the blocks it meets are
+// consecutive: its waves mark them in an LDS copy of the bitmap words they
+// fall into (a wave's rows of one tile lie in one block, so the ballot of a
+// tile is one block's), and the words that are not zero go out at the end --
+// at most one vector atomic per workgroup and bitmap word, none for empty
+// blocks.
+constexpr int kOccInFlight = 4;
+constexpr int kOccLdsWords = 130;  // bitmap words a workgroup's rows can meet (launch_row_occupancy sizes the grid)
+constexpr int kOccRowsPerWG = 131072;
+
+__global__ __launch_bounds__(kCensusThreads) void row_occupancy_kernel(const uint32_t* __restrict__ plane, int64_t pitch,
+                                                                       int32_t chunks, int32_t lo, int32_t hi, int lgx,
+                                                                       int64_t per, unsigned* bits, int32_t nwords) {
+    __shared__ unsigned s_bits[kOccLdsWords];
+    const int bx = 1 << lgx, by = kCensusThreads >> lgx;
+    const int tx = threadIdx.x & (bx - 1), ty = threadIdx.x >> lgx;
+    const int32_t xtiles = (chunks + bx - 1) >> lgx;
+    const int64_t items = (int64_t)((hi - lo + by - 1) / by) * xtiles;
+    const int64_t it_lo = min((int64_t)blockIdx.x * per, items), it_hi = min(items, it_lo + per);
+    // the bitmap word of the first block this workgroup can meet
+    const int32_t w0 = (int32_t)(((lo + (it_lo / xtiles) * by) / kOccupancyBlock) >> 5);
+    for (int t = threadIdx.x; t < kOccLdsWords; t += kCensusThreads) s_bits[t] = 0u;
+    __syncthreads();
+    int32_t marked = -1;  // the block this wave marked last
+    for (int64_t it0 = it_lo; it0 < it_hi; it0 += kOccInFlight) {
+        uint4 v[kOccInFlight];
+        int32_t row[kOccInFlight];
+#pragma unroll
+        for (int u = 0; u < kOccInFlight; ++u) {
+            const int64_t it = it0 + u;
+            const int64_t yt = it / xtiles;
+            const int32_t xt = (int32_t)(it - yt * xtiles);
+            const int64_t r = lo + yt * by + ty;
+            const int32_t q = xt * bx + tx;
+            row[u] = (int32_t)min(r, (int64_t)INT32_MAX);
+            v[u] = make_uint4(0u, 0u, 0u, 0u);  // outside the rows: nothing alive
+            if (it < it_hi && r < hi && q < chunks)
+                v[u] = *reinterpret_cast<const uint4*>(plane + r * pitch + 4 * (int64_t)q);
+        }
+#pragma unroll
+        for (int u = 0; u < kOccInFlight; ++u) {
+            const bool any = __ballot((v[u].x | v[u].y | v[u].z | v[u].w) != 0u) != 0ull;  // wave-uniform
+            const int32_t blk = __builtin_amdgcn_readfirstlane(row[u] / kOccupancyBlock);
+            if (!any || blk == marked) continue;
+            marked = blk;
+            const int32_t idx = (blk >> 5) - w0;
+            if ((threadIdx.x & (kWaveLanes - 1)) == 0 && (unsigned)idx < (unsigned)kOccLdsWords)
+                atomicOr(&s_bits[idx], 1u << (blk & 31));
+        }
+    }
+    __syncthreads();
+    for (int t = threadIdx.x; t < kOccLdsWords; t += kCensusThreads) {
+        const unsigned b = s_bits[t];
+        if (b != 0u && w0 + t < nwords) atomicOr(bits + w0 + t, b);
+    }
+}
+
 int grid_for(int64_t total) { return (int)std::max<int64_t>(1, std::min<int64_t>((total + 255) / 256, 2048)); }
 
 uint32_t last_word_mask(int64_t w) { return w % 32 ? (uint32_t)((1ull << (w % 32)) - 1ull) : 0xFFFFFFFFu; }
@@ -484,6 +550,28 @@ hipError_t launch_census(const uint32_t* plane, int64_t pitch, int32_t wwords, i
 
 hipError_t launch_census_fold(unsigned long long* slots, unsigned long long* out, hipStream_t stream) {
     return launch_kernel(census_fold_kernel, dim3(1), dim3(kWaveLanes), stream, slots, out);
+}
+
+hipError_t launch_row_occupancy(const uint32_t* plane, int64_t pitch, int32_t wwords, int32_t lo, int32_t hi,
+                                uint32_t* bits, int32_t nwords, hipStream_t stream) {
+    // 16-byte loads, as the census; every block of the rows has its bit in the bitmap
+    if (pitch % 4 != 0 || pitch < (wwords + 3) / 4 * 4 || wwords < 1 || lo < 0 || lo >= hi || lo % kOccupancyBlock != 0 ||
+        (reinterpret_cast<uintptr_t>(plane) & 15) != 0 || !bits ||
+        ((int64_t)hi + kOccupancyBlock - 1) / kOccupancyBlock > 32 * (int64_t)nwords)
+        return hipErrorInvalidValue;
+    const int32_t chunks = (wwords + 3) / 4;
+    int lgx = 0;
+    while (lgx < 8 && (1 << lgx) < chunks) ++lgx;
+    const int bx = 1 << lgx, by = kCensusThreads >> lgx;
+    const int64_t xtiles = (chunks + bx - 1) / bx;
+    const int64_t items = (int64_t)((hi - lo + by - 1) / by) * xtiles;
+    // memory-bound, as the census: at most 2048 workgroups, more only where one would otherwise meet more
+    // rows than its LDS bitmap covers (kOccLdsWords)
+    static_assert((kOccRowsPerWG + 3 * kCensusThreads) / kOccupancyBlock + 1 <= 32 * (kOccLdsWords - 1), "LDS bitmap");
+    const int64_t blocks = std::max<int64_t>({1, std::min<int64_t>(items, 2048), ((int64_t)hi - lo) / kOccRowsPerWG + 1});
+    const int64_t per = (items + blocks - 1) / blocks;
+    return launch_kernel(row_occupancy_kernel, dim3((unsigned)((items + per - 1) / per)), dim3(kCensusThreads), stream,
+                         plane, pitch, chunks, lo, hi, lgx, per, reinterpret_cast<unsigned*>(bits), nwords);
 }
 
 hipError_t launch_region_gather(const uint32_t* src, int64_t pitch, int32_t wwords, int ilv, int32_t nrows, int64_t x0,

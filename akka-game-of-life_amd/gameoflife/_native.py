@@ -96,6 +96,17 @@ class GolCensusResult(ctypes.Structure):
     ]
 
 
+class GolActiveStats(ctypes.Structure):
+    _fields_ = [
+        ("passes", ctypes.c_uint64),
+        ("sparse_passes", ctypes.c_uint64),
+        ("rows_stepped", ctypes.c_uint64),
+        ("rows_cleared", ctypes.c_uint64),
+        ("scans", ctypes.c_uint64),
+        ("rows_scanned", ctypes.c_uint64),
+    ]
+
+
 # gol_write_region modes (include/gol.h GOL_REGION_*)
 GOL_REGION_COPY = 0
 GOL_REGION_OR = 1
@@ -167,6 +178,9 @@ _SIGNATURES = {
     "gol_write_region": (_c.c_int, [_vp, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_int64, _u32p, _c.c_int64,
                                     _c.c_int32]),
     "gol_density": (_c.c_int, [_vp, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_int32, _u32p, _c.c_int64]),
+    "gol_set_active_rows": (_c.c_int, [_vp, _c.c_int32]),
+    "gol_active_stats_read": (_c.c_int, [_vp, ctypes.POINTER(GolActiveStats), _c.c_int32]),
+    "gol_active_rows": (_c.c_int, [_vp, ctypes.POINTER(_c.c_int64), _c.c_int32, ctypes.POINTER(_c.c_int32)]),
 }
 
 

@@ -21,7 +21,7 @@ class GolEngine:
 
     def __init__(self, width: int, height: int, *, topology: str = "torus",
                  rule: Rule | str = "life", device: int = 0, row0: int = 0,
-                 rows: int | None = None, vis: tuple[int, int] | None = None):
+                 rows: int | None = None, vis: tuple[int, int] | None = None, active_rows: bool = False):
         self.rule = rule_by_name(rule) if isinstance(rule, str) else rule
         self.topology = topology
         topo = {"torus": N.GOL_TORUS, "ref-clipped": N.GOL_REF_CLIPPED}[topology]
@@ -42,6 +42,8 @@ class GolEngine:
         self.row0, self.rows = row0, cfg.rows
         self.wwords = (width + 31) // 32
         self.device = device
+        if active_rows:
+            self.set_active_rows(True)
 
     # -- lifecycle ---------------------------------------------------------
     def close(self) -> None:
@@ -314,6 +316,30 @@ class GolEngine:
         """Performance knobs only (gol_set_tuning): rows per band, generations
         per HBM pass (1..12), words per lane (1/2/4, 0 = auto)."""
         self._chk(N.lib.gol_set_tuning(self._h, band_rows, gens_per_pass, words_per_lane))
+
+    def set_active_rows(self, enable: bool = True) -> None:
+        """Active-row stepping (gol_set_active_rows): step only the row runs
+        that can hold a live cell.  A performance knob: results never depend
+        on it.  With it on, an unhashed step() may wait for a device scan."""
+        self._chk(N.lib.gol_set_active_rows(self._h, 1 if enable else 0))
+
+    def active_stats(self, reset: bool = False) -> dict:
+        """gol_active_stats_read: passes run with the mode on, how many of
+        them stepped row runs, and the rows stepped, cleared and scanned."""
+        st = N.GolActiveStats()
+        self._chk(N.lib.gol_active_stats_read(self._h, ctypes.byref(st), 1 if reset else 0))
+        return {k: getattr(st, k) for k, _ in N.GolActiveStats._fields_}
+
+    def active_rows(self) -> list[tuple[int, int]] | None:
+        """The runs [lo, hi) of global rows outside which the current board is
+        known dead (gol_active_rows); None when nothing is known."""
+        n = ctypes.c_int32(0)
+        self._chk(N.lib.gol_active_rows(self._h, None, 0, ctypes.byref(n)))
+        if n.value < 0:
+            return None
+        buf = (ctypes.c_int64 * (2 * max(n.value, 1)))()
+        self._chk(N.lib.gol_active_rows(self._h, buf, n.value, ctypes.byref(n)))
+        return [(buf[2 * k], buf[2 * k + 1]) for k in range(n.value)]
 
 
 class ShardGroup:

@@ -53,7 +53,8 @@ extern "C" {
  * those of row-major boards (clipped, odd word counts) differ from version 1.
  * The entry points and structs are those of version 1.  gol_census,
  * gol_read_region, gol_write_region and gol_density were added without a new
- * version: additive entry points change nothing a version-2 caller relies on. */
+ * version: additive entry points change nothing a version-2 caller relies on.
+ * So were gol_set_active_rows, gol_active_stats_read and gol_active_rows. */
 #define GOL_ABI_VERSION 2
 
 /* Return codes. */
@@ -159,7 +160,10 @@ int gol_load(gol_ctx* ctx, const uint32_t* packed, int64_t host_pitch_words);
  * hold `generations` entries (gol_step_ex checks a capacity).  With a
  * communicator attached, G halo rows are exchanged over RCCL before every pass
  * of G generations.  Asynchronous when hashes_out is NULL (call gol_sync to
- * wait). */
+ * wait) -- except with active-row stepping on (gol_set_active_rows): a pass
+ * that scans the board for its live rows waits for the scan, and with it for
+ * every pass queued before it, so the call may return only once most of its
+ * work is done. */
 int gol_step(gol_ctx* ctx, uint32_t generations, uint64_t* hashes_out);
 
 /* gol_step with the capacity of hashes_out (entries): GOL_EINVAL, and no
@@ -429,7 +433,9 @@ int gol_profile_clock(gol_ctx* ctx, double* ghz);
  *   exchange_exposed_ms / pass_tail_ms: per pass, how long after the end of
  *       its interior launch the exchange (resp. the boundary launch) ended,
  *       0 if before, summed: the part of the exchange the interior did not
- *       hide, and the pass's whole critical path beyond the interior. */
+ *       hide (so at most the exchange itself, where the interior ended before
+ *       the exchange began), and the pass's whole critical path beyond the
+ *       interior. */
 typedef struct gol_profile_stats {
     double kernel_ms;
     uint64_t launches;
@@ -474,6 +480,39 @@ int gol_runtime_info_get(gol_runtime_info* out);
  * clipped visibility) would spill registers to scratch and are not built
  * (the planner caps planned passes of such a tuning at 7). */
 int gol_set_tuning(gol_ctx* ctx, int32_t band_rows, int32_t gens_per_pass, int32_t words_per_lane);
+
+/* Active-row stepping, a knob like the tuning: results
+ * never depend on it -- boards, epochs, hashes, census, snapshots and
+ * checkpoints are bit-identical with it on or off.  enable: 0 off (the
+ * default of a new context), 1 on; GOL_EINVAL otherwise.  With it on, a pass
+ * steps only the row runs that can hold a live cell (the rows written through
+ * gol_write_region or found by a device scan, grown by the pass depth) and
+ * clears what the destination plane held elsewhere, so a small pattern on a
+ * huge board advances in time proportional to the pattern.  Rows only, and
+ * only on a context stepped whole: while a communicator, a loopback ring or a
+ * shard group is attached, and for rules with birth on 0 neighbours, the mode
+ * is accepted and every pass steps the whole plane as before.  A board that
+ * is live all over falls back to whole-plane passes and is scanned again
+ * after ever longer waits (4, 16, 64, then every 256 passes).  May be switched
+ * at any epoch. */
+int gol_set_active_rows(gol_ctx* ctx, int32_t enable);
+
+typedef struct gol_active_stats {
+    uint64_t passes;        /* passes run since the last reset, mode on            */
+    uint64_t sparse_passes; /* ... of them stepped as row runs                      */
+    uint64_t rows_stepped;  /* output rows launched, summed over passes             */
+    uint64_t rows_cleared;  /* rows zeroed in the destination plane                 */
+    uint64_t scans;         /* device scans for live rows ...                       */
+    uint64_t rows_scanned;  /* ... and the rows they read                           */
+} gol_active_stats;
+/* The counters of this context; reset != 0 zeroes them after reading. */
+int gol_active_stats_read(gol_ctx* ctx, gol_active_stats* out, int32_t reset);
+
+/* Diagnostic: the runs [lo, hi) (global rows) outside which the current plane
+ * is known dead, as at most max_runs pairs in lo_hi_pairs (may be NULL when
+ * max_runs is 0) and their number in *count; *count = -1 when nothing is known
+ * (after gol_seed, gol_load, a sharded pass ...).  Kept in either mode. */
+int gol_active_rows(gol_ctx* ctx, int64_t* lo_hi_pairs, int32_t max_runs, int32_t* count);
 
 /* Diagnostic: the pass depths (generations fused per HBM pass) gol_step would
  * use to advance `generations` generations (at most 1024: gol_step plans per
