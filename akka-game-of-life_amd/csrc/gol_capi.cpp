@@ -411,6 +411,32 @@ int gol_step_ex(gol_ctx* ctx, uint32_t generations, uint64_t* hashes_out, size_t
     return gol_step(ctx, generations, hashes_out);
 }
 
+int gol_step_series(gol_ctx* ctx, uint32_t generations, uint64_t* hashes_out, uint64_t* populations_out,
+                    size_t capacity) {
+    if (!ctx) return set_err(nullptr, GOL_EINVAL, "null context");
+    if ((hashes_out || populations_out) && capacity < generations)
+        return set_err(ctx, GOL_EINVAL, "the series arrays hold %zu entries, %u generations requested", capacity,
+                       generations);
+    if (!populations_out) return gol_step(ctx, generations, hashes_out);
+    if (int rc = bind(ctx)) return rc;
+    const int series = hashes_out ? kSeriesHash | kSeriesPop : kSeriesPop;
+    constexpr uint32_t kChunk = 1024;
+    for (uint32_t g0 = 0; g0 < generations; g0 += kChunk) {
+        const uint32_t n = std::min(kChunk, generations - g0);
+        if (int rc = ensure_slots(ctx, n)) return rc;
+        const size_t per = (size_t)gol::kHashGenStride;
+        if (int rc = clear_slots(ctx, n)) return rc;
+        uint32_t g = 0;
+        // any series is planned as a hashed step is
+        for (const int G : plan_passes(ctx, n, true)) {
+            if (int rc = one_pass(ctx, G, ctx->slots + g * per, series)) return rc;
+            g += (uint32_t)G;
+        }
+        if (int rc = read_series(ctx, n, hashes_out ? hashes_out + g0 : nullptr, populations_out + g0)) return rc;
+    }
+    return GOL_OK;
+}
+
 int gol_epoch(const gol_ctx* ctx, uint64_t* epoch) {
     if (!ctx || !epoch) return set_err(nullptr, GOL_EINVAL, "null argument");
     *epoch = ctx->epoch;

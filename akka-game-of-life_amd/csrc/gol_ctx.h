@@ -102,7 +102,8 @@ struct gol_ctx {
     unsigned long long* slots = nullptr;  // [gens][kHashSlots * kHashSlotStride]
     uint32_t slots_gens = 0;
     uint32_t slots_clean = 0;  // leading generations of `slots` known to be zero (left so by read_hashes)
-    unsigned long long* host_folded = nullptr;      // [slots_gens] page-locked, mapped: per-generation sums
+    unsigned long long* host_folded = nullptr;      // [2][slots_gens] page-locked, mapped: per-generation hash
+                                                    // sums, then (gol_step_series) populations
     unsigned long long* host_folded_dev = nullptr;  // ... its device address (fold_kernel stores there)
     uint64_t epoch = 0;
     hipStream_t compute = nullptr, comm = nullptr;
@@ -236,10 +237,13 @@ int clear_slots(gol_ctx* ctx, uint32_t gens);
 // hashes into out[], folded on the device straight into mapped host memory,
 // the accumulators cleared again; synchronises.
 int read_hashes(gol_ctx* ctx, uint32_t gens, uint64_t* out);
+// The same after a chunk of series passes (PassLaunch::series with kSeriesPop):
+// the hashes and the populations, each into its array unless null.
+int read_series(gol_ctx* ctx, uint32_t gens, uint64_t* hashes_out, uint64_t* populations_out);
 int lane_words(const gol_ctx* ctx, int gens);
 // The kernel instance a pass of `gens` generations runs on this context: the
 // one place that derives it (and so a pass's strip width, gol::strip_words).
-gol::StepInstance step_instance(const gol_ctx* ctx, int gens, bool hashed);
+gol::StepInstance step_instance(const gol_ctx* ctx, int gens, bool hashed, bool pop = false);
 int64_t resident_waves(const gol_ctx* ctx, const gol::StepInstance& k);
 // Load every step kernel instance the context can launch at its current
 // tuning (the occupancy query of an instance loads its code object).
@@ -252,6 +256,10 @@ struct PlaneGeom {
     int64_t grow0;
 };
 
+// The per-generation series a pass with accumulators (slots) sums into them:
+// the state hash (gol_step), the population (gol_step_series), or both.
+enum Series { kSeriesHash = 1, kSeriesPop = 2 };
+
 // One launch of a pass: `gens` generations over local row ranges
 // [lo[0], hi[0]) (+ [lo[1], hi[1]) if n == 2).
 struct PassLaunch {
@@ -263,6 +271,7 @@ struct PassLaunch {
     int64_t halo_stride = 0;
     bool wrap_y = false;                 // unsharded torus: rows wrap inside the plane, no halo read
     unsigned long long* slots = nullptr;  // hash accumulators of these generations, or null (unhashed)
+    int series = kSeriesHash;             // what a pass with slots accumulates (Series bits)
     int n = 1;
     int32_t lo[2] = {0, 0}, hi[2] = {0, 0};
     int prof_kind = kProfMain;
@@ -275,11 +284,12 @@ struct PassLaunch {
 // small-board test).
 int strip_count(const gol_ctx* ctx, gol::StepInstance k, bool halo_lanes = false);
 int launch_ranges(gol_ctx* ctx, const PassLaunch& launch);
-int sharded_interior(gol_ctx* ctx, int G, unsigned long long* slots, bool has_up, bool has_down);
+int sharded_interior(gol_ctx* ctx, int G, unsigned long long* slots, bool has_up, bool has_down,
+                     int series = kSeriesHash);
 int sharded_boundary(gol_ctx* ctx, int G, unsigned long long* slots, bool has_up, bool has_down,
-                     const hipEvent_t* halo_ready, int nready);
+                     const hipEvent_t* halo_ready, int nready, int series = kSeriesHash);
 int sharded_pass_kernels(gol_ctx* ctx, int G, unsigned long long* slots, bool has_up, bool has_down,
-                         const hipEvent_t* halo_ready, int nready);
+                         const hipEvent_t* halo_ready, int nready, int series = kSeriesHash);
 int depth_cap(const gol_ctx* ctx);
 std::vector<int> plan_passes(const gol_ctx* ctx, uint32_t n, bool hashed);
 
@@ -294,7 +304,7 @@ struct HaloOp {
     int peer;
 };
 
-int one_pass(gol_ctx* ctx, int G, unsigned long long* slots);
+int one_pass(gol_ctx* ctx, int G, unsigned long long* slots, int series = kSeriesHash);
 void loop_leave(gol_ctx* ctx);
 
 // What the writers of a plane owe the active-row invariant (LiveRows):
@@ -311,6 +321,9 @@ inline void live_add(gol_ctx* ctx, int p, int64_t lo, int64_t hi) {
 // ---- shard groups (gol_group.cpp) ------------------------------------------
 
 size_t group_size(const gol_group* g);
+// gol_group_step_partials, or with populations_out the series call (no partials).
+int group_step(gol_group* g, uint32_t generations, uint64_t* hashes_out, uint64_t* partials_out,
+               uint64_t* populations_out);
 int64_t group_min_rows(const gol_group* g);
 
 // ---- profiling (gol_profile.cpp) -------------------------------------------

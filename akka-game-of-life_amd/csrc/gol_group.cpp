@@ -32,7 +32,7 @@ int group_fail(gol_group* g, const gol_ctx* s, int rc) {
 //    neighbours' pulls (ev_halo of all three), so its next pass cannot
 //    overwrite rows a neighbour is still reading, and its next pull cannot
 //    overwrite halo rows its boundary kernels still read.
-int group_pass(gol_group* g, int G, const std::vector<unsigned long long*>& slots) {
+int group_pass(gol_group* g, int G, const std::vector<unsigned long long*>& slots, int series) {
     const int n = (int)g->shards.size();
     for (gol_ctx* s : g->shards) {
         if (int rc = bind(s)) return group_fail(g, s, rc);
@@ -68,7 +68,8 @@ int group_pass(gol_group* g, int G, const std::vector<unsigned long long*>& slot
         if (has_up) ready[nr++] = up->ev_halo;
         if (has_down) ready[nr++] = dn->ev_halo;
         if (int rc = bind(s)) return group_fail(g, s, rc);
-        if (int rc = sharded_pass_kernels(s, G, slots.empty() ? nullptr : slots[k], has_up, has_down, ready, nr))
+        if (int rc =
+                sharded_pass_kernels(s, G, slots.empty() ? nullptr : slots[k], has_up, has_down, ready, nr, series))
             return group_fail(g, s, rc);
     }
     for (gol_ctx* s : g->shards) {
@@ -157,6 +158,24 @@ int gol_group_step(gol_group* g, uint32_t generations, uint64_t* hashes_out) {
 }
 
 int gol_group_step_partials(gol_group* g, uint32_t generations, uint64_t* hashes_out, uint64_t* partials_out) {
+    return group_step(g, generations, hashes_out, partials_out, nullptr);
+}
+
+int gol_group_step_series(gol_group* g, uint32_t generations, uint64_t* hashes_out, uint64_t* populations_out,
+                          size_t capacity) {
+    if (!g) return set_err(nullptr, GOL_EINVAL, "null group");
+    if ((hashes_out || populations_out) && capacity < generations) {
+        g->err = "gol_group_step_series: the arrays hold " + std::to_string(capacity) + " entries, " +
+                 std::to_string(generations) + " generations requested";
+        return GOL_EINVAL;
+    }
+    return group_step(g, generations, hashes_out, nullptr, populations_out);
+}
+
+}  // extern "C"
+
+int golc::group_step(gol_group* g, uint32_t generations, uint64_t* hashes_out, uint64_t* partials_out,
+                     uint64_t* populations_out) {
     if (!g) return set_err(nullptr, GOL_EINVAL, "null group");
     if (partials_out && !hashes_out) {
         g->err = "partials_out needs hashes_out";
@@ -168,11 +187,13 @@ int gol_group_step_partials(gol_group* g, uint32_t generations, uint64_t* hashes
     const size_t per = (size_t)gol::kHashGenStride;
     const int n = (int)g->shards.size();
     constexpr uint32_t kChunk = 1024;
-    std::vector<uint64_t> part;
+    std::vector<uint64_t> part, ppart;
+    const bool any = hashes_out || populations_out;
+    const int series = populations_out ? (hashes_out ? kSeriesHash | kSeriesPop : kSeriesPop) : kSeriesHash;
     for (uint32_t g0 = 0; g0 < generations; g0 += kChunk) {
         const uint32_t cnt = std::min(kChunk, generations - g0);
         std::vector<unsigned long long*> base;
-        if (hashes_out) {
+        if (any) {
             for (gol_ctx* s : g->shards) {
                 if (int rc = bind(s)) return group_fail(g, s, rc);
                 if (int rc = ensure_slots(s, cnt)) return group_fail(g, s, rc);
@@ -181,20 +202,30 @@ int gol_group_step_partials(gol_group* g, uint32_t generations, uint64_t* hashes
             }
         }
         uint32_t done = 0;
-        for (const int G : plan_passes(g->shards[0], cnt, hashes_out != nullptr)) {
+        for (const int G : plan_passes(g->shards[0], cnt, any)) {  // any series: the hashed plan
             std::vector<unsigned long long*> slots;
             for (unsigned long long* b : base) slots.push_back(b + done * per);
-            if (int rc = group_pass(g, G, slots)) return rc;
+            if (int rc = group_pass(g, G, slots, series)) return rc;
             done += (uint32_t)G;
         }
-        if (hashes_out) {
-            for (uint32_t k = 0; k < cnt; ++k) hashes_out[g0 + k] = 0;
+        if (any) {
+            for (uint32_t k = 0; k < cnt; ++k) {
+                if (hashes_out) hashes_out[g0 + k] = 0;
+                if (populations_out) populations_out[g0 + k] = 0;
+            }
             part.resize(cnt);
+            ppart.resize(cnt);
             for (int k = 0; k < n; ++k) {
                 gol_ctx* s = g->shards[k];
                 if (int rc = bind(s)) return group_fail(g, s, rc);
-                if (int rc = read_hashes(s, cnt, part.data())) return group_fail(g, s, rc);
-                for (uint32_t j = 0; j < cnt; ++j) hashes_out[g0 + j] += part[j];
+                if (populations_out) {
+                    if (int rc = read_series(s, cnt, part.data(), ppart.data())) return group_fail(g, s, rc);
+                    for (uint32_t j = 0; j < cnt; ++j) populations_out[g0 + j] += ppart[j];
+                } else if (int rc = read_hashes(s, cnt, part.data())) {
+                    return group_fail(g, s, rc);
+                }
+                if (hashes_out)
+                    for (uint32_t j = 0; j < cnt; ++j) hashes_out[g0 + j] += part[j];
                 if (partials_out)
                     std::copy(part.begin(), part.end(), partials_out + (size_t)k * generations + g0);
             }
@@ -202,6 +233,8 @@ int gol_group_step_partials(gol_group* g, uint32_t generations, uint64_t* hashes
     }
     return GOL_OK;
 }
+
+extern "C" {
 
 int gol_group_sync(gol_group* g) {
     if (!g) return set_err(nullptr, GOL_EINVAL, "null group");

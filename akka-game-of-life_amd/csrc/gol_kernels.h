@@ -21,6 +21,8 @@ constexpr int kWavesPerWG = GOL_WAVES_PER_WG;  // waves per workgroup (256-threa
 constexpr int kHashSlots = 64;   // sharded hash accumulators (one cache line each)
 constexpr int kHashSlotStride = 8;  // u64 per slot => 64 B apart
 constexpr int kHashGenStride = kHashSlots * kHashSlotStride;  // u64 per generation
+constexpr int kPopSlotWord = 1;     // a slot's population count (series instances): the u64 after its hash sum
+static_assert(kPopSlotWord < kHashSlotStride, "the population count shares the hash sum's line");
 constexpr int kMaxGensPerPass = 12;  // temporal blocking depth supported by the kernels
 // Deepest pass of the 16-byte-lane (words_per_lane = 4) generic-rule and
 // clipped instances that keeps every variable in registers: deeper ones spill
@@ -85,7 +87,7 @@ struct StepParams {
     uint32_t* nxt;             // local row 0 of the next plane
     const uint32_t* halo_top;  // rows -G .. -1 (halo_stride apart)
     const uint32_t* halo_bot;  // rows rows .. rows+G-1
-    unsigned long long* hash_slots;  // G * kHashGenStride u64, or null
+    unsigned long long* hash_slots;  // G * kHashGenStride u64 (hash sums, population counts), or null
     int64_t pitch;             // words between rows (multiple of 64)
     int64_t grow0;             // global row of local row 0
     int64_t vis_rows;          // global rows [0, vis_rows) are visible (clipped)
@@ -132,11 +134,14 @@ inline bool whole_row_fits(int vec, int gens, bool life, bool clipped, int ilv, 
 // generations per pass; ilv: the plane's interleave (1 row-major, 2 pairs; vec
 // a multiple of it); life: B3/S23 fast path (torus only); hash: fuse the
 // per-generation state hash; clipped: reference geometry; whole_row: one strip
-// is the whole torus row (whole_row_fits).  Multi-generation passes at
+// is the whole torus row (whole_row_fits); pop: fuse the per-generation
+// population count (with or without the hash; the population-series instances,
+// kernels of their own).  Multi-generation passes at
 // vec <= 2 run the horizontal-first kernel, at vec = 4 the vertical-first one.
 struct StepInstance {
     int vec, gens, ilv;
     bool life, hash, clipped, whole_row;
+    bool pop;
 };
 
 // Strip geometry of a launch: words covered per wave (multi-generation strips
@@ -170,6 +175,11 @@ hipError_t launch_hash(const uint32_t* plane, int64_t pitch, int32_t wwords, int
 // clears; `folded` may be mapped host memory (8 bytes per generation cross
 // PCIe instead of the 4 KiB of accumulators).
 hipError_t launch_fold(unsigned long long* slots, uint32_t gens, unsigned long long* folded, hipStream_t stream);
+// The same after passes of the population-series instances: folded[g] the
+// hash sum and folded_pop[g] the population of generation g; both words of
+// every slot are cleared.
+hipError_t launch_fold_series(unsigned long long* slots, uint32_t gens, unsigned long long* folded,
+                              unsigned long long* folded_pop, hipStream_t stream);
 
 // DPP / lane-shift self test: out[64*4] (see gol_selftest in gol_capi.cpp).
 hipError_t launch_selftest(const uint32_t* in, uint32_t* out, hipStream_t stream);

@@ -109,6 +109,27 @@ __global__ __launch_bounds__(kWaveLanes) void fold_kernel(unsigned long long* sl
     if (lane == 0) folded[g] = h;  // vector store
 }
 
+// fold_kernel for the population-series instances: both words of a slot.
+__global__ __launch_bounds__(kWaveLanes) void fold_series_kernel(unsigned long long* slots, uint32_t gens,
+                                                                 unsigned long long* folded,
+                                                                 unsigned long long* folded_pop) {
+    const uint32_t g = blockIdx.x;
+    const int lane = threadIdx.x;
+    unsigned long long* a = slots + (size_t)g * kHashGenStride + (size_t)lane * kHashSlotStride;
+    unsigned long long h = a[0], n = a[kPopSlotWord];
+    a[0] = 0ull;
+    a[kPopSlotWord] = 0ull;
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        h += __shfl_xor(h, off, kWaveLanes);
+        n += __shfl_xor(n, off, kWaveLanes);
+    }
+    if (lane == 0) {  // vector stores
+        folded[g] = h;
+        folded_pop[g] = n;
+    }
+}
+
 __global__ void selftest_kernel(const uint32_t* in, uint32_t* out) {
     const int lane = threadIdx.x;
     const uint32_t v = in[lane];
@@ -127,7 +148,9 @@ namespace {
 template <int... I>
 StepKernel step_kernel_of(const StepInstance& k, std::integer_sequence<int, I...>) {
     static constexpr StepKernel (*kAtDepth[])(const StepInstance&) = {&step_kernel_at<I + 1>...};
-    return k.gens >= 1 && k.gens <= kMaxGensPerPass ? kAtDepth[k.gens - 1](k) : nullptr;
+    static constexpr StepKernel (*kSeriesAtDepth[])(const StepInstance&) = {&step_series_kernel_at<I + 1>...};
+    if (k.gens < 1 || k.gens > kMaxGensPerPass) return nullptr;
+    return k.pop ? kSeriesAtDepth[k.gens - 1](k) : kAtDepth[k.gens - 1](k);
 }
 StepKernel step_kernel_of(const StepInstance& k) {
     return step_kernel_of(k, std::make_integer_sequence<int, kMaxGensPerPass>{});
@@ -183,6 +206,12 @@ hipError_t launch_hash(const uint32_t* plane, int64_t pitch, int32_t wwords, int
 hipError_t launch_fold(unsigned long long* slots, uint32_t gens, unsigned long long* folded, hipStream_t stream) {
     if (gens == 0) return hipSuccess;
     return launch_kernel(fold_kernel, dim3(gens), dim3(kWaveLanes), stream, slots, gens, folded);
+}
+
+hipError_t launch_fold_series(unsigned long long* slots, uint32_t gens, unsigned long long* folded,
+                              unsigned long long* folded_pop, hipStream_t stream) {
+    if (gens == 0) return hipSuccess;
+    return launch_kernel(fold_series_kernel, dim3(gens), dim3(kWaveLanes), stream, slots, gens, folded, folded_pop);
 }
 
 hipError_t launch_selftest(const uint32_t* in, uint32_t* out, hipStream_t stream) {

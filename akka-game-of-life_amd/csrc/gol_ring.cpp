@@ -379,7 +379,7 @@ void loop_leave(gol_ctx* ctx) {
 // One pass of G generations (temporal blocking, G <= kMaxGensPerPass) of a
 // stand-alone or RCCL-sharded context.  slots: the hash accumulators of these
 // G generations (G * kHashGenStride), or null.
-int one_pass(gol_ctx* ctx, int G, unsigned long long* slots) {
+int one_pass(gol_ctx* ctx, int G, unsigned long long* slots, int series) {
     uint32_t* cur = ctx->plane[ctx->cur];
     uint32_t* nxt = ctx->plane[ctx->cur ^ 1];
     const int32_t rows = (int32_t)ctx->rows;
@@ -394,11 +394,13 @@ int one_pass(gol_ctx* ctx, int G, unsigned long long* slots) {
         L.halo_top = L.halo_bot = ctx->zero_row;
         L.wrap_y = torus;
         L.slots = slots;
+        L.series = series;
         // Active-row stepping.  Without birth on 0
         // neighbours a dead cell with no live neighbour stays dead on both
         // topologies, so the live cells of every generation of the pass lie
         // within the current plane's runs grown by G rows: stepping those rows
-        // alone gives the same plane and, summed over them, the same hashes.
+        // alone gives the same plane and, summed over them, the same hashes
+        // and populations (a row that is not launched is dead and adds 0).
         const bool quiet = (ctx->birth & 1u) == 0;  // nothing is born in empty space
         bool stepped = false;
         if (ctx->active_on && quiet) {
@@ -438,7 +440,7 @@ int one_pass(gol_ctx* ctx, int G, unsigned long long* slots) {
         // the communicator.
         HIP_CHECK(ctx, hipEventRecord(ctx->ev_ready, ctx->compute));
         const size_t evs_before = ctx->evs_used;
-        const int rc_interior = sharded_interior(ctx, G, slots, has_up, has_down);
+        const int rc_interior = sharded_interior(ctx, G, slots, has_up, has_down, series);
         // the interior launch's event pair (profiling; -1 if it has none in this fold window)
         int iref = (ctx->prof && ctx->evs_used == evs_before + 1) ? (int)evs_before : -1;
         HIP_CHECK(ctx, hipStreamWaitEvent(ctx->comm, ctx->ev_ready, 0));
@@ -479,7 +481,7 @@ int one_pass(gol_ctx* ctx, int G, unsigned long long* slots) {
         // only after the boundary kernels, which wait for it.
         HIP_CHECK(ctx, hipEventRecord(ctx->ev_halo, ctx->comm));
         const size_t evs_mid = ctx->evs_used;
-        int rc = sharded_boundary(ctx, G, slots, has_up, has_down, &ctx->ev_halo, 1);
+        int rc = sharded_boundary(ctx, G, slots, has_up, has_down, &ctx->ev_halo, 1, series);
         if (rc) return rc;
         if (ctx->prof && ctx->evs_used == evs_mid + 1 && ctx->evs[evs_mid].kind == kProfBoundary && iref >= 0 &&
             (int)evs_mid > iref)

@@ -74,7 +74,8 @@ int ensure_slots(gol_ctx* ctx, uint32_t gens) {
     if (old_host) HIP_CHECK(ctx, hipHostFree(old_host));
     HIP_CHECK(ctx, hipMalloc(&ctx->slots, (size_t)gens * gol::kHashGenStride * sizeof(unsigned long long)));
     // coherent: fold_kernel's stores reach host memory without a cache flush
-    HIP_CHECK(ctx, hipHostMalloc((void**)&ctx->host_folded, (size_t)gens * sizeof(unsigned long long),
+    // twice: the hash sums, then the populations of a series call (read_series)
+    HIP_CHECK(ctx, hipHostMalloc((void**)&ctx->host_folded, 2 * (size_t)gens * sizeof(unsigned long long),
                                  hipHostMallocMapped | hipHostMallocCoherent));
     HIP_CHECK(ctx, hipHostGetDevicePointer((void**)&ctx->host_folded_dev, ctx->host_folded, 0));
     ctx->slots_gens = gens;  // only once every buffer exists
@@ -102,6 +103,17 @@ int read_hashes(gol_ctx* ctx, uint32_t gens, uint64_t* out) {
     return GOL_OK;
 }
 
+int read_series(gol_ctx* ctx, uint32_t gens, uint64_t* hashes_out, uint64_t* populations_out) {
+    const size_t pop0 = ctx->slots_gens;  // the populations' half of the mapped words
+    HIP_CHECK(ctx, gol::launch_fold_series(ctx->slots, gens, ctx->host_folded_dev, ctx->host_folded_dev + pop0,
+                                           ctx->compute));
+    HIP_CHECK(ctx, hipStreamSynchronize(ctx->compute));
+    if (hashes_out) std::memcpy(hashes_out, ctx->host_folded, gens * sizeof(uint64_t));
+    if (populations_out) std::memcpy(populations_out, ctx->host_folded + pop0, gens * sizeof(uint64_t));
+    ctx->slots_clean = gens;
+    return GOL_OK;
+}
+
 // Words per lane for a pass of `gens` generations.  Multi-generation strips
 // carry 62 output lanes, so a row of w words needs ceil(w / (62 v)) strips;
 // prefer 16-byte lanes unless 8-byte lanes waste clearly fewer lanes.
@@ -118,13 +130,14 @@ int lane_words(const gol_ctx* ctx, int gens) {
     return ok2 || ctx->ilv == 2 ? 2 : 1;
 }
 
-gol::StepInstance step_instance(const gol_ctx* ctx, int gens, bool hashed) {
+gol::StepInstance step_instance(const gol_ctx* ctx, int gens, bool hashed, bool pop) {
     gol::StepInstance k{};
     k.vec = lane_words(ctx, gens);
     k.gens = gens;
     k.ilv = ctx->ilv;
     k.life = life_torus(ctx);
     k.hash = hashed;
+    k.pop = pop;
     k.clipped = ctx->topology == GOL_REF_CLIPPED;
     k.whole_row =
         gol::whole_row_fits(k.vec, gens, k.life, k.clipped, k.ilv, ctx->topology == GOL_TORUS, ctx->wwords);
@@ -133,8 +146,8 @@ gol::StepInstance step_instance(const gol_ctx* ctx, int gens, bool hashed) {
 
 // Resident waves on the whole GPU for a launch (cached occupancy query).
 int64_t resident_waves(const gol_ctx* ctx, const gol::StepInstance& k) {
-    const int key = (((((k.vec * 16 + k.gens) * 2 + k.life) * 2 + k.hash) * 2 + k.clipped) * 2 + k.whole_row) * 8 +
-                    k.ilv;
+    const int key = ((((((k.vec * 16 + k.gens) * 2 + k.life) * 2 + k.hash) * 2 + k.clipped) * 2 + k.whole_row) * 8 +
+                     k.ilv) * 2 + k.pop;
     auto it = ctx->occupancy_cache.find(key);
     if (it != ctx->occupancy_cache.end()) return it->second;
     const int64_t waves = (int64_t)gol::resident_blocks_per_cu(k) * gol::kWavesPerWG * ctx->num_cus;
@@ -144,7 +157,9 @@ int64_t resident_waves(const gol_ctx* ctx, const gol::StepInstance& k) {
 
 void preload_instances(gol_ctx* ctx) {
     // unbuilt instances (16-byte generic / clipped lanes deeper than
-    // kMaxGensVec4Generic, gol_stencil.h kBuilt) report 0 blocks without a load
+    // kMaxGensVec4Generic, gol_stencil.h kBuilt) report 0 blocks without a load.
+    // The population-series instances are left to their first use: their code
+    // objects would lengthen every gol_create for the callers of one entry point.
     for (int G = 1; G <= gol::kMaxGensPerPass; ++G)
         for (int h = 0; h < 2; ++h) (void)resident_waves(ctx, step_instance(ctx, G, h != 0));
 }
@@ -163,7 +178,9 @@ int strip_count(const gol_ctx* ctx, gol::StepInstance k, bool halo_lanes) {
 // profiling events: it is the dominant kernel.
 int launch_ranges(gol_ctx* ctx, const PassLaunch& L) {
     const hipStream_t stream = L.stream ? L.stream : ctx->compute;
-    const gol::StepInstance k = step_instance(ctx, L.gens, L.slots != nullptr);
+    const bool acc = L.slots != nullptr;
+    const gol::StepInstance k =
+        step_instance(ctx, L.gens, acc && (L.series & kSeriesHash) != 0, acc && (L.series & kSeriesPop) != 0);
     const int strips = strip_count(ctx, k);
     const golplan::BandPlan bp = golplan::band_plan(L.n, L.lo, L.hi, strips, L.gens, resident_waves(ctx, k),
                                                     ctx->band_rows, tail_env, gol::kWavesPerWG);
@@ -218,7 +235,8 @@ int launch_ranges(gol_ctx* ctx, const PassLaunch& L) {
 // at the plane's pitch and the hash slots.  A missing neighbour (clipped board
 // ends) reads dead rows: zero_row holds kMaxGensPerPass of them at the halo
 // pitch.  The caller sets the ranges, the profiling kind and the stream.
-static PassLaunch sharded_launch(gol_ctx* ctx, int G, unsigned long long* slots, bool has_up, bool has_down) {
+static PassLaunch sharded_launch(gol_ctx* ctx, int G, unsigned long long* slots, bool has_up, bool has_down,
+                                 int series) {
     PassLaunch L;
     L.gens = G;
     L.cur = ctx->plane[ctx->cur];
@@ -227,16 +245,17 @@ static PassLaunch sharded_launch(gol_ctx* ctx, int G, unsigned long long* slots,
     L.halo_bot = has_down ? ctx->halo_bot : ctx->zero_row;
     L.halo_stride = ctx->pitch;
     L.slots = slots;
+    L.series = series;
     return L;
 }
 
 // The interior rows [G, rows - G) of a sharded pass on the compute stream:
 // they read no halo, so they are enqueued before the exchange (one_pass) and
 // run while it is in flight.  Shards of <= 2G rows have no interior.
-int sharded_interior(gol_ctx* ctx, int G, unsigned long long* slots, bool has_up, bool has_down) {
+int sharded_interior(gol_ctx* ctx, int G, unsigned long long* slots, bool has_up, bool has_down, int series) {
     const int32_t rows = (int32_t)ctx->rows;
     if (rows <= 2 * G) return GOL_OK;
-    PassLaunch L = sharded_launch(ctx, G, slots, has_up, has_down);
+    PassLaunch L = sharded_launch(ctx, G, slots, has_up, has_down, series);
     L.lo[0] = G;
     L.hi[0] = rows - G;
     return launch_ranges(ctx, L);
@@ -249,9 +268,9 @@ int sharded_interior(gol_ctx* ctx, int G, unsigned long long* slots, bool has_up
 // of after it; the compute stream then waits for it, so the next pass, a
 // snapshot or a hash sees the whole plane.
 int sharded_boundary(gol_ctx* ctx, int G, unsigned long long* slots, bool has_up, bool has_down,
-                     const hipEvent_t* halo_ready, int nready) {
+                     const hipEvent_t* halo_ready, int nready, int series) {
     const int32_t rows = (int32_t)ctx->rows;
-    PassLaunch L = sharded_launch(ctx, G, slots, has_up, has_down);
+    PassLaunch L = sharded_launch(ctx, G, slots, has_up, has_down, series);
     if (rows > 2 * G) {
         // The exchange events follow this pass's ev_ready, recorded on the
         // compute stream after the previous pass's boundary rows: every
@@ -279,9 +298,9 @@ int sharded_boundary(gol_ctx* ctx, int G, unsigned long long* slots, bool has_up
 // in-process group): the interior rows, then the boundary rows after
 // `halo_ready`.
 int sharded_pass_kernels(gol_ctx* ctx, int G, unsigned long long* slots, bool has_up, bool has_down,
-                         const hipEvent_t* halo_ready, int nready) {
-    if (int rc = sharded_interior(ctx, G, slots, has_up, has_down)) return rc;
-    return sharded_boundary(ctx, G, slots, has_up, has_down, halo_ready, nready);
+                         const hipEvent_t* halo_ready, int nready, int series) {
+    if (int rc = sharded_interior(ctx, G, slots, has_up, has_down, series)) return rc;
+    return sharded_boundary(ctx, G, slots, has_up, has_down, halo_ready, nready, series);
 }
 
 // Deepest pass the context may run.  Every shard of a ring must pick the

@@ -570,6 +570,48 @@ __device__ __forceinline__ void hash_flush_gens(unsigned long long (&acc)[G], un
     }
 }
 
+// Fused population series: the live cells of a
+// generation's stored words, summed where its hash is summed and under the
+// same gates -- a band's own rows (wave-uniform: a select or a uniform
+// branch, as the hash of the same kernel takes it; never a lane branch),
+// owning lanes only.  v_bcnt_u32_b32 adds a word's count to its accumulator; a
+// lane's count of one generation fits 32 bits (32 VEC cells per band row),
+// and so does a wave's (the band rows of a launch number far below 2^20).
+template <int VEC>
+__device__ __forceinline__ uint32_t pop_row(const Words<VEC>& o, uint32_t sum) {
+#pragma unroll
+    for (int j = 0; j < VEC; ++j) sum += (uint32_t)__builtin_popcount(o.w[j]);
+    return sum;
+}
+
+// The G per-lane counts of a pass -> wave sums -> workgroup sums -> one atomic
+// per generation into the second word of the workgroup's hash slot (the line
+// the hash of that generation uses 8 bytes of; fold_series_kernel folds and
+// clears both).  Every lane of the workgroup must arrive.
+template <int G>
+__device__ __forceinline__ void pop_flush_gens(uint32_t (&cnt)[G], unsigned long long* slots, int lane,
+                                               int wave_in_wg) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1)
+#pragma unroll
+        for (int s = 0; s < G; ++s) cnt[s] += (uint32_t)__shfl_xor((int)cnt[s], off, kWaveLanes);
+    __shared__ uint32_t pop_part[kWavesPerWG][G];
+    if (lane == 0) {
+#pragma unroll
+        for (int s = 0; s < G; ++s) pop_part[wave_in_wg][s] = cnt[s];
+    }
+    __syncthreads();
+    const int s = threadIdx.x;
+    if (s < G) {
+        unsigned long long t = 0;
+#pragma unroll
+        for (int w = 0; w < kWavesPerWG; ++w) t += pop_part[w][s];
+        atomicAdd(slots + (size_t)s * kHashGenStride + (size_t)(blockIdx.x % kHashSlots) * kHashSlotStride +
+                      kPopSlotWord,
+                  t);
+    }
+}
+
 // --------------------------------------------------------------------------
 // One generation per pass.
 // --------------------------------------------------------------------------
@@ -582,18 +624,36 @@ __device__ __forceinline__ void hash_flush_gens(unsigned long long (&acc)[G], un
 // -3..-8 % at G = 6 with non-temporal stores, profiles/r01_bandwidth.txt).
 constexpr bool kG1NtStores = true;
 
-template <int VEC, bool LIFE, bool HASH, bool CLIPPED, int ILV>
+// The population-series instances are instances of the
+// same kernel templates: their last template argument, the plane's interleave
+// (1 or 2), carries kKindSeries as well.  The plain instances keep their
+// arguments -- and with them their symbols and, every POP block being an
+// `if constexpr`, their code; the series instances get symbols of their own
+// (and live in code objects of their own, gol_step.hip).  A __global__
+// wrapper of another name over a shared __forceinline__ body was tried first
+// and moved the parameter block of every kernel to scratch (row_lo[rg] and
+// its like index it at run time): +176 B of scratch and a wave or two per
+// SIMD less on the pre-existing instances.
+constexpr int kKindSeries = 4;
+constexpr int kind_ilv(int kind) { return kind & 3; }
+constexpr bool kind_pop(int kind) { return (kind & kKindSeries) != 0; }
+
+template <int VEC, bool LIFE, bool HASH, bool CLIPPED, int KIND>
 __global__ __launch_bounds__(kWaveLanes* kWavesPerWG) void step_kernel(const StepParams p) {
+    constexpr int ILV = kind_ilv(KIND);
+    constexpr bool POP = kind_pop(KIND);
     const int lane = threadIdx.x & (kWaveLanes - 1);
     const int wave_in_wg = __builtin_amdgcn_readfirstlane(threadIdx.x / kWaveLanes);
     const WaveTile tile = wave_tile(p, xcd_block(blockIdx.x, gridDim.x, p.xcd_chunk) * kWavesPerWG + wave_in_wg);
     const ClockStart clk0 = clock_probe_begin(p.clk);
     const int rg = tile.range, strip = tile.strip, bandi = tile.band;
     unsigned long long acc = 0;
+    uint32_t pcnt[1] = {0u};
 
     if (bandi < p.nbands[rg]) {
         HashAcc<VEC> hacc;
         hash_clear(hacc);
+        uint32_t pacc = 0u;
         const int r_begin = p.row_lo[rg] + bandi * p.band[rg];
         const int r_end = min(r_begin + p.band[rg], p.row_hi[rg]);
         const int nrows = r_end - r_begin;
@@ -678,6 +738,9 @@ __global__ __launch_bounds__(kWaveLanes* kWavesPerWG) void step_kernel(const Ste
             if constexpr (HASH) {
                 if (in_band) hash_row<VEC, ILV>(p.grow0 + r, o, odd_lane, hacc);
             }
+            if constexpr (POP) {
+                if (in_band) pacc = pop_row<VEC>(o, pacc);
+            }
         };
         auto step_i = [&](int i, int u, bool in_band) {
             const int ua = u % kRing, uc = (u + 1) % kRing, ub = (u + 2) % kRing;
@@ -729,16 +792,20 @@ __global__ __launch_bounds__(kWaveLanes* kWavesPerWG) void step_kernel(const Ste
             }
         }
         if constexpr (HASH) acc = hash_lane_total(hacc, col, active);
+        if constexpr (POP) pcnt[0] = active ? pacc : 0u;
     }
     if constexpr (HASH) hash_flush(acc, p.hash_slots, lane, wave_in_wg);
+    if constexpr (POP) pop_flush_gens<1>(pcnt, p.hash_slots, lane, wave_in_wg);
     clock_probe_end(p.clk, clk0);
 }
 
 // --------------------------------------------------------------------------
 // G generations per pass (temporal blocking).
 // --------------------------------------------------------------------------
-template <int VEC, int G, bool LIFE, bool HASH, bool CLIPPED, int ILV>
+template <int VEC, int G, bool LIFE, bool HASH, bool CLIPPED, int KIND>
 __global__ __launch_bounds__(kWaveLanes* kWavesPerWG) void multistep_kernel(const StepParams p) {
+    constexpr int ILV = kind_ilv(KIND);
+    constexpr bool POP = kind_pop(KIND);
     static_assert(G >= 2 && G <= kMaxGensPerPass, "G");
     static_assert(G < 32 * VEC, "halo lane narrower than the garbage front");
     constexpr int kOut = (kWaveLanes - 2) * VEC;  // output words per strip
@@ -748,8 +815,12 @@ __global__ __launch_bounds__(kWaveLanes* kWavesPerWG) void multistep_kernel(cons
     const ClockStart clk0 = clock_probe_begin(p.clk);
     const int rg = tile.range, strip = tile.strip, bandi = tile.band;
     unsigned long long acc[G];
+    uint32_t pcnt[G];
 #pragma unroll
-    for (int s = 0; s < G; ++s) acc[s] = 0;
+    for (int s = 0; s < G; ++s) {
+        acc[s] = 0;
+        pcnt[s] = 0u;
+    }
 
     if (bandi < p.nbands[rg]) {
         const int r_begin = p.row_lo[rg] + bandi * p.band[rg];
@@ -832,6 +903,9 @@ __global__ __launch_bounds__(kWaveLanes* kWavesPerWG) void multistep_kernel(cons
                     if constexpr (HASH) {
                         if (own_row) hash_row<VEC, ILV>(p.grow0 + brow(m), o, odd_lane, hacc[s - 1]);
                     }
+                    if constexpr (POP) {
+                        if (own_row) pcnt[s - 1] = pop_row<VEC>(o, pcnt[s - 1]);
+                    }
                     // stage s+1: stream row q-s-1 from stage-s rows q-s-2, q-s-1, q-s
                     apply(st[s - 1][((u - s - 2) % 3 + 3) % 3], st[s - 1][((u - s - 1) % 3 + 3) % 3],
                           st[s - 1][((u - s) % 3 + 3) % 3], m - 1, o);
@@ -840,6 +914,9 @@ __global__ __launch_bounds__(kWaveLanes* kWavesPerWG) void multistep_kernel(cons
                     store_row<VEC>(p.nxt + (int64_t)r * p.pitch, own_row, p.wwords * 4, lcol, owns, o);
                     if constexpr (HASH) {
                         if (own_row) hash_row<VEC, ILV>(p.grow0 + r, o, odd_lane, hacc[G - 1]);
+                    }
+                    if constexpr (POP) {
+                        if (own_row) pcnt[G - 1] = pop_row<VEC>(o, pcnt[G - 1]);
                     }
                 }
             }
@@ -855,9 +932,16 @@ __global__ __launch_bounds__(kWaveLanes* kWavesPerWG) void multistep_kernel(cons
 #pragma unroll
             for (int s = 0; s < G; ++s) acc[s] = hash_lane_total(hacc[s], col, owns);
         }
+        if constexpr (POP) {
+#pragma unroll
+            for (int s = 0; s < G; ++s) pcnt[s] = owns ? pcnt[s] : 0u;
+        }
     }
     if constexpr (HASH) {
         hash_flush_gens<G>(acc, p.hash_slots, lane, wave_in_wg);
+    }
+    if constexpr (POP) {
+        pop_flush_gens<G>(pcnt, p.hash_slots, lane, wave_in_wg);
     }
     clock_probe_end(p.clk, clk0);
 }
@@ -956,8 +1040,10 @@ constexpr bool kPairRows = LIFE && !CLIPPED && VEC <= 2;
 
 // WR: a whole-row wave (gol_kernels.h whole_row_fits) -- 64 output lanes,
 // the row's wrap a wave rotate, one strip.
-template <int VEC, int G, bool LIFE, bool HASH, bool CLIPPED, int ILV, bool WR = false>
+template <int VEC, int G, bool LIFE, bool HASH, bool CLIPPED, int KIND, bool WR = false>
 __global__ __launch_bounds__(kWaveLanes* kWavesPerWG) void multistep_hg_kernel(const StepParams p) {
+    constexpr int ILV = kind_ilv(KIND);
+    constexpr bool POP = kind_pop(KIND);
     static_assert(VEC <= 2, "16-byte lanes run the vertical-first kernel");
     static_assert(G >= 2 && G <= kMaxGensPerPass, "G");
     static_assert(G < 32 * VEC, "halo lane narrower than the garbage front");
@@ -973,6 +1059,13 @@ __global__ __launch_bounds__(kWaveLanes* kWavesPerWG) void multistep_hg_kernel(c
 #pragma unroll
     for (int s = 0; s < G; ++s) acc[s] = 0;
     __shared__ unsigned long long hash_lds[HASH ? kWavesPerWG * G * HashAcc<VEC>::kGroups * kWaveLanes : 1];
+    // The population counts live in LDS for the hash sums' reason (hash_row_lds):
+    // one u32 per lane and generation, added to with ds_add_u32 (no return)
+    // instead of G more live registers.
+    __shared__ uint32_t pop_lds[POP ? kWavesPerWG * G * kWaveLanes : 1];
+    uint32_t pcnt[G];
+#pragma unroll
+    for (int s = 0; s < G; ++s) pcnt[s] = 0u;
 
     if (bandi < p.nbands[rg]) {
         const int r_begin = p.row_lo[rg] + bandi * p.band[rg];
@@ -989,8 +1082,9 @@ __global__ __launch_bounds__(kWaveLanes* kWavesPerWG) void multistep_hg_kernel(c
         // nothing of its own and toggles no register bits, and this kernel is
         // held at its power limit (DESIGN.md §4 "Clock").  DPP reads a
         // switched-off lane as zero (bound_ctrl), as it reads past lane 63.
-        // The hashed instances keep every lane: hash_flush reduces across all 64.
-        if constexpr (!HASH && !WR) {
+        // The hashed instances keep every lane: hash_flush reduces across all 64
+        // (and so do the population instances).
+        if constexpr (!HASH && !POP && !WR) {
             if (lane > (nout + VEC - 1) / VEC + 1) return;
         }
         int lcol;
@@ -1016,6 +1110,12 @@ __global__ __launch_bounds__(kWaveLanes* kWavesPerWG) void multistep_hg_kernel(c
         if constexpr (HASH) {
 #pragma unroll
             for (int k = 0; k < G * kNP; ++k) hsum[k * kWaveLanes] = 0ull;
+        }
+        // this lane's LDS counts: generation s at psum[s * kWaveLanes]
+        uint32_t* psum = pop_lds + (size_t)wave_in_wg * G * kWaveLanes + lane;
+        if constexpr (POP) {
+#pragma unroll
+            for (int k = 0; k < G; ++k) psum[k * kWaveLanes] = 0u;
         }
         const bool up = (bandi & 1) != 0;
         auto brow = [&](int m) -> int { return up ? r_end - 1 + G - m : r_begin - G + m; };
@@ -1104,6 +1204,20 @@ __global__ __launch_bounds__(kWaveLanes* kWavesPerWG) void multistep_hg_kernel(c
                 if constexpr (HASH) {
                     hash_row_lds<VEC, ILV>(kae[s], kao[s], o, odd_lane, hsum + (s - 1) * kNP * kWaveLanes);
                 }
+                if constexpr (POP) {
+                    // own_row is wave-uniform.  The B3/S23 instances take it as a
+                    // select and stay one straight-line block (a branch costs the
+                    // whole-row G = 10 instance its third wave: 169 VGPRs); the
+                    // generic-rule and clipped ones take a uniform branch, whose
+                    // block boundary keeps the scheduler from the 230-256 VGPRs
+                    // their unhashed siblings run at.
+                    if constexpr (LIFE) {
+                        const uint32_t t = pop_row<VEC>(o, 0u);
+                        atomicAdd(psum + (s - 1) * kWaveLanes, own_row ? t : 0u);
+                    } else {
+                        if (own_row) atomicAdd(psum + (s - 1) * kWaveLanes, pop_row<VEC>(o, 0u));
+                    }
+                }
                 if (s < G) {
                     arrive<VEC, CLIPPED, ILV, WR>(o, vis(m), cmask, hr[s][((u - s) % 3 + 3) % 3]);
                 } else {
@@ -1140,9 +1254,16 @@ __global__ __launch_bounds__(kWaveLanes* kWavesPerWG) void multistep_hg_kernel(c
                 acc[s] = hash_lane_total(h, col, owns);
             }
         }
+        if constexpr (POP) {
+#pragma unroll
+            for (int s = 0; s < G; ++s) pcnt[s] = owns ? psum[s * kWaveLanes] : 0u;
+        }
     }
     if constexpr (HASH) {
         hash_flush_gens<G>(acc, p.hash_slots, lane, wave_in_wg);
+    }
+    if constexpr (POP) {
+        pop_flush_gens<G>(pcnt, p.hash_slots, lane, wave_in_wg);
     }
     clock_probe_end(p.clk, clk0);
 }
@@ -1158,23 +1279,27 @@ constexpr bool kBuilt = G == 1 || VEC <= 2 || (LIFE && !CLIPPED) || G <= kMaxGen
 
 // The kernel of one instance, or null: not built, or `whole_row` where the
 // instance has no whole-row kernel (the host layer asks for neither).
-template <int VEC, int G, bool LIFE, bool HASH, bool CLIPPED, int ILV>
+// SERIES: the instance's population-series sibling (StepInstance::pop; HASH:
+// together with the hash, or population alone), built under the same rule.
+template <int VEC, int G, bool LIFE, bool HASH, bool CLIPPED, int ILV, bool SERIES = false>
 StepKernel kernel_one(bool whole_row) {
+    constexpr int KIND = ILV | (SERIES ? kKindSeries : 0);
     if constexpr (!kBuilt<VEC, G, LIFE, CLIPPED>) {
         return nullptr;
     } else if constexpr (VEC == kWholeRowVec && G == kWholeRowGens && LIFE && !CLIPPED && ILV == 2) {
-        return whole_row ? multistep_hg_kernel<VEC, G, LIFE, HASH, CLIPPED, ILV, true>
-                         : multistep_hg_kernel<VEC, G, LIFE, HASH, CLIPPED, ILV>;
+        return whole_row ? multistep_hg_kernel<VEC, G, LIFE, HASH, CLIPPED, KIND, true>
+                         : multistep_hg_kernel<VEC, G, LIFE, HASH, CLIPPED, KIND>;
     } else if (whole_row) {
         return nullptr;
     } else if constexpr (G == 1) {
-        return step_kernel<VEC, LIFE, HASH, CLIPPED, ILV>;
+        return step_kernel<VEC, LIFE, HASH, CLIPPED, KIND>;
     } else if constexpr (VEC <= 2) {
-        return multistep_hg_kernel<VEC, G, LIFE, HASH, CLIPPED, ILV>;
+        return multistep_hg_kernel<VEC, G, LIFE, HASH, CLIPPED, KIND>;
     } else {
-        return multistep_kernel<VEC, G, LIFE, HASH, CLIPPED, ILV>;
+        return multistep_kernel<VEC, G, LIFE, HASH, CLIPPED, KIND>;
     }
 }
+
 
 // The instances a launch can select: clipped boards (generic rule, row-major
 // words), tori (B3/S23 fast path or generic rule) in row-major or pair layout
@@ -1197,15 +1322,18 @@ auto dispatch_kind(bool life, bool hash, bool clipped, int ilv, F&& f) {
     return hash ? f(N{}, T{}, N{}, I1{}) : f(N{}, N{}, N{}, I1{});
 }
 
-// The kernel of instance `k` at depth G (k.gens is not looked at).
-template <int G>
+// The kernel of instance `k` at depth G (k.gens is not looked at); SERIES:
+// of the population-series instances (k.pop set) or of the plain ones (not
+// set), which live in different code objects (gol_step.hip).
+template <int G, bool SERIES = false>
 StepKernel kernel_at_depth(const StepInstance& k) {
+    if (k.pop != SERIES) return nullptr;
     auto of_vec = [&](auto V) -> StepKernel {
         constexpr int VEC = decltype(V)::value;
         if (VEC % k.ilv != 0) return nullptr;  // checked by the host layer
         return dispatch_kind<VEC>(k.life, k.hash, k.clipped, k.ilv, [&](auto L, auto H, auto C, auto I) {
-            return kernel_one<VEC, G, decltype(L)::value, decltype(H)::value, decltype(C)::value, decltype(I)::value>(
-                k.whole_row);
+            return kernel_one<VEC, G, decltype(L)::value, decltype(H)::value, decltype(C)::value, decltype(I)::value,
+                              SERIES>(k.whole_row);
         });
     };
     switch (k.vec) {
@@ -1223,5 +1351,9 @@ StepKernel kernel_at_depth(const StepInstance& k) {
 // kernels of a depth live in that depth's code object.
 template <int G>
 StepKernel step_kernel_at(const StepInstance& k);
+// ... and dev::kernel_at_depth<G, true>, the population-series instances of
+// depth G, in that depth's series object.
+template <int G>
+StepKernel step_series_kernel_at(const StepInstance& k);
 
 }  // namespace gol

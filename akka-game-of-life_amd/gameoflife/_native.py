@@ -133,6 +133,7 @@ _SIGNATURES = {
     "gol_load": (_c.c_int, [_vp, _u32p, _c.c_int64]),
     "gol_step": (_c.c_int, [_vp, _c.c_uint32, _u64p]),
     "gol_step_ex": (_c.c_int, [_vp, _c.c_uint32, _u64p, _c.c_size_t]),
+    "gol_step_series": (_c.c_int, [_vp, _c.c_uint32, _u64p, _u64p, _c.c_size_t]),
     "gol_epoch": (_c.c_int, [_vp, _u64p]),
     "gol_sync": (_c.c_int, [_vp]),
     "gol_hash": (_c.c_int, [_vp, _u64p]),
@@ -165,6 +166,7 @@ _SIGNATURES = {
     "gol_group_create": (_c.c_int, [ctypes.POINTER(_vp), ctypes.POINTER(_vp), _c.c_int]),
     "gol_group_step": (_c.c_int, [_vp, _c.c_uint32, _u64p]),
     "gol_group_step_partials": (_c.c_int, [_vp, _c.c_uint32, _u64p, _u64p]),
+    "gol_group_step_series": (_c.c_int, [_vp, _c.c_uint32, _u64p, _u64p, _c.c_size_t]),
     "gol_group_sync": (_c.c_int, [_vp]),
     "gol_group_last_error": (_c.c_char_p, [_vp]),
     "gol_group_destroy": (None, [_vp]),

@@ -115,8 +115,18 @@ class GolEngine:
         """A page-locked (rows, wwords) uint32 buffer for snapshots / loads."""
         return host_array((self.rows, self.wwords))
 
-    def step(self, generations: int = 1, hashes: bool = False):
-        """Advance; returns the per-generation partial hashes (uint64) if asked."""
+    def step(self, generations: int = 1, hashes: bool = False, populations: bool = False):
+        """Advance; returns the per-generation partial hashes (uint64) if asked.
+        populations=True: the per-generation populations of this shard's rows
+        (uint64, gol_step_series: counted inside the step kernels, what
+        population() would give after each generation), or (hashes,
+        populations) when both are asked."""
+        if populations:
+            pop = np.zeros(generations, dtype=np.uint64)
+            out = np.zeros(generations, dtype=np.uint64) if hashes else None
+            self._chk(N.lib.gol_step_series(self._h, generations, out.ctypes.data_as(N._u64p) if hashes else None,
+                                            pop.ctypes.data_as(N._u64p), pop.size))
+            return (out, pop) if hashes else pop
         if hashes:
             out = np.zeros(generations, dtype=np.uint64)
             self._chk(N.lib.gol_step_ex(self._h, generations, out.ctypes.data_as(N._u64p), out.size))
@@ -358,10 +368,22 @@ class ShardGroup:
         if rc != N.GOL_OK:
             raise N.GolError(rc, (N.lib.gol_group_last_error(self._h) or b"").decode())
 
-    def step(self, generations: int = 1, hashes: bool = False, partials: bool = False):
+    def step(self, generations: int = 1, hashes: bool = False, partials: bool = False, populations: bool = False):
         """Advance every shard; returns the global per-generation hashes if
         asked, and with partials=True also every shard's partials as a
-        (shards, generations) array (gol_group_step_partials)."""
+        (shards, generations) array (gol_group_step_partials).
+        populations=True: the board's per-generation populations
+        (gol_group_step_series), or (hashes, populations) when both are asked;
+        not together with partials."""
+        if partials and populations:
+            raise ValueError("ShardGroup.step: partials and populations cannot be asked together")
+        if populations:
+            pop = np.zeros(generations, dtype=np.uint64)
+            out = np.zeros(generations, dtype=np.uint64) if hashes else None
+            self._chk(N.lib.gol_group_step_series(self._h, generations,
+                                                  out.ctypes.data_as(N._u64p) if hashes else None,
+                                                  pop.ctypes.data_as(N._u64p), pop.size))
+            return (out, pop) if hashes else pop
         if partials:
             out = np.zeros(generations, dtype=np.uint64)
             part = np.zeros((len(self.shards), generations), dtype=np.uint64)

@@ -54,7 +54,8 @@ extern "C" {
  * The entry points and structs are those of version 1.  gol_census,
  * gol_read_region, gol_write_region and gol_density were added without a new
  * version: additive entry points change nothing a version-2 caller relies on.
- * So were gol_set_active_rows, gol_active_stats_read and gol_active_rows. */
+ * So were gol_set_active_rows, gol_active_stats_read and gol_active_rows, and
+ * gol_step_series and gol_group_step_series (the fused population series). */
 #define GOL_ABI_VERSION 2
 
 /* Return codes. */
@@ -171,6 +172,21 @@ int gol_step(gol_ctx* ctx, uint32_t generations, uint64_t* hashes_out);
  * `generations` entries.  The form a JVM binding calls with a direct buffer's
  * capacity. */
 int gol_step_ex(gol_ctx* ctx, uint32_t generations, uint64_t* hashes_out, size_t hashes_capacity);
+
+/* gol_step that also returns a population series, summed inside the step
+ * kernels where the hash is summed: populations_out[g]
+ * is the number of live stored cells of the shard's rows after generation
+ * g + 1 of the call -- what gol_census would report as `population` at that
+ * epoch (on GOL_REF_CLIPPED the sink row and column included) -- without a
+ * second read of the plane and at the pass depths of a hashed step.
+ * hashes_out[g] is what gol_step writes.  Either array may be NULL; `capacity`
+ * is the entries of each array that is not.  Shards combine by sum, as the
+ * hashes do (gol_comm_allreduce_u64).  With both arrays NULL the call is
+ * gol_step(ctx, generations, NULL), asynchronous included; otherwise it
+ * synchronises.  GOL_EINVAL, and no generation advanced, for a NULL context or
+ * an array of fewer than `generations` entries; generations = 0 is GOL_OK. */
+int gol_step_series(gol_ctx* ctx, uint32_t generations, uint64_t* hashes_out, uint64_t* populations_out,
+                    size_t capacity);
 
 /* Light-cone replay of a re-spawned shard, alone.  Replaces the reference's
  * re-born cell catching up from its neighbours' never-pruned histories
@@ -395,6 +411,11 @@ int gol_group_step(gol_group* group, uint32_t generations, uint64_t* hashes_out)
  * g (hashes_out required).  The fault path keeps them to check a re-spawned
  * shard's replayed partials against the recorded global hashes. */
 int gol_group_step_partials(gol_group* group, uint32_t generations, uint64_t* hashes_out, uint64_t* partials_out);
+/* gol_step_series over the group: the global hashes and the global
+ * populations (the shards' sums); either array may be NULL, `capacity` as
+ * there. */
+int gol_group_step_series(gol_group* group, uint32_t generations, uint64_t* hashes_out, uint64_t* populations_out,
+                          size_t capacity);
 int gol_group_sync(gol_group* group);
 const char* gol_group_last_error(const gol_group* group);
 void gol_group_destroy(gol_group* group);
