@@ -2,9 +2,9 @@
 // lifetime, seeding and loading, stepping (gol_step: the pass plan of
 // gol_schedule.cpp run by gol_ring.cpp's one_pass), state hashes, tuning and
 // the small host-side entry points.  The other entry points live in
-// gol_ring.cpp, gol_group.cpp, gol_checkpoint.cpp, gol_profile.cpp and
-// gol_region.cpp; the
-// unit map and the reference correspondence are in gol_ctx.h.
+// gol_ring.cpp, gol_loopback.cpp, gol_active.cpp, gol_group.cpp,
+// gol_checkpoint.cpp, gol_profile.cpp and gol_region.cpp; the unit map and the
+// reference correspondence are in gol_ctx.h.
 #include <dlfcn.h>
 
 #include <algorithm>
@@ -144,13 +144,13 @@ void destroy_impl(gol_ctx* c) {
     for (hipEvent_t ev : {c->ev_ready, c->ev_halo, c->ev_edge, c->ev_snap_ready, c->ev_snap_done})
         if (ev) hip_note(hipEventDestroy(ev), "destroy: hipEventDestroy");
     for (void* p : {(void*)c->snap, (void*)c->clk_buf, (void*)c->plane[0], (void*)c->plane[1], (void*)c->halo_top,
-                    (void*)c->halo_bot, (void*)c->zero_row, (void*)c->slots, (void*)c->region_stage,
-                    (void*)c->census_slots, (void*)c->density_grid, (void*)c->active_bits})
+                    (void*)c->halo_bot, (void*)c->zero_row})
         if (p) hip_note(hipFree(p), "destroy: hipFree");
-    if (c->host_folded) hip_note(hipHostFree(c->host_folded), "destroy: hipHostFree");
-    if (c->census_host) hip_note(hipHostFree(c->census_host), "destroy: hipHostFree");
-    if (c->density_host) hip_note(hipHostFree(c->density_host), "destroy: hipHostFree");
-    if (c->active_host) hip_note(hipHostFree(c->active_host), "destroy: hipHostFree");
+    hip_note(c->sums.release(), "destroy: hash accumulators");
+    hip_note(c->region_stage.release(), "destroy: window staging buffer");
+    hip_note(c->census.release(), "destroy: census accumulators");
+    hip_note(c->density.release(), "destroy: density map");
+    hip_note(c->active_bits.release(), "destroy: active-row bitmap");
     for (hipStream_t st : {c->compute, c->comm, c->edge, c->xfer})
         if (st) hip_note(hipStreamDestroy(st), "destroy: hipStreamDestroy");
     delete c;
@@ -377,30 +377,23 @@ int gol_load(gol_ctx* ctx, const uint32_t* packed, int64_t host_pitch_words) {
     return GOL_OK;
 }
 
+// Every step of a context by itself: the chunk loop over one_pass, summing the
+// series the caller gave arrays for (none: no accumulators, no fold).
+static int step_ctx(gol_ctx* ctx, uint32_t generations, uint64_t* hashes_out, uint64_t* populations_out) {
+    if (int rc = bind(ctx)) return rc;
+    const int series = (hashes_out ? kSeriesHash : 0) | (populations_out ? kSeriesPop : 0);
+    return step_chunks(
+        ctx, generations, series != 0, [&](uint32_t n) { return prepare_sums(ctx, n); },
+        [&](int G, uint32_t g) { return one_pass(ctx, G, pass_sums(ctx, series, g)); },
+        [&](uint32_t g0, uint32_t n) {
+            return read_sums(ctx, n, hashes_out ? hashes_out + g0 : nullptr,
+                             populations_out ? populations_out + g0 : nullptr);
+        });
+}
+
 int gol_step(gol_ctx* ctx, uint32_t generations, uint64_t* hashes_out) {
     if (!ctx) return set_err(nullptr, GOL_EINVAL, "null context");
-    if (int rc = bind(ctx)) return rc;
-    if (generations == 0) return GOL_OK;
-    constexpr uint32_t kChunk = 1024;
-    if (!hashes_out) {
-        for (uint32_t g0 = 0; g0 < generations; g0 += kChunk)
-            for (const int G : plan_passes(ctx, std::min(kChunk, generations - g0), false))
-                if (int rc = one_pass(ctx, G, nullptr)) return rc;
-        return GOL_OK;
-    }
-    for (uint32_t g0 = 0; g0 < generations; g0 += kChunk) {
-        const uint32_t n = std::min(kChunk, generations - g0);
-        if (int rc = ensure_slots(ctx, n)) return rc;
-        const size_t per = (size_t)gol::kHashGenStride;
-        if (int rc = clear_slots(ctx, n)) return rc;
-        uint32_t g = 0;
-        for (const int G : plan_passes(ctx, n, true)) {
-            if (int rc = one_pass(ctx, G, ctx->slots + g * per)) return rc;
-            g += (uint32_t)G;
-        }
-        if (int rc = read_hashes(ctx, n, hashes_out + g0)) return rc;
-    }
-    return GOL_OK;
+    return step_ctx(ctx, generations, hashes_out, nullptr);
 }
 
 int gol_step_ex(gol_ctx* ctx, uint32_t generations, uint64_t* hashes_out, size_t hashes_capacity) {
@@ -417,24 +410,7 @@ int gol_step_series(gol_ctx* ctx, uint32_t generations, uint64_t* hashes_out, ui
     if ((hashes_out || populations_out) && capacity < generations)
         return set_err(ctx, GOL_EINVAL, "the series arrays hold %zu entries, %u generations requested", capacity,
                        generations);
-    if (!populations_out) return gol_step(ctx, generations, hashes_out);
-    if (int rc = bind(ctx)) return rc;
-    const int series = hashes_out ? kSeriesHash | kSeriesPop : kSeriesPop;
-    constexpr uint32_t kChunk = 1024;
-    for (uint32_t g0 = 0; g0 < generations; g0 += kChunk) {
-        const uint32_t n = std::min(kChunk, generations - g0);
-        if (int rc = ensure_slots(ctx, n)) return rc;
-        const size_t per = (size_t)gol::kHashGenStride;
-        if (int rc = clear_slots(ctx, n)) return rc;
-        uint32_t g = 0;
-        // any series is planned as a hashed step is
-        for (const int G : plan_passes(ctx, n, true)) {
-            if (int rc = one_pass(ctx, G, ctx->slots + g * per, series)) return rc;
-            g += (uint32_t)G;
-        }
-        if (int rc = read_series(ctx, n, hashes_out ? hashes_out + g0 : nullptr, populations_out + g0)) return rc;
-    }
-    return GOL_OK;
+    return step_ctx(ctx, generations, hashes_out, populations_out);
 }
 
 int gol_epoch(const gol_ctx* ctx, uint64_t* epoch) {
@@ -454,11 +430,10 @@ int gol_sync(gol_ctx* ctx) {
 int gol_hash(gol_ctx* ctx, uint64_t* hash_out) {
     if (!ctx || !hash_out) return set_err(ctx, GOL_EINVAL, "null argument");
     if (int rc = bind(ctx)) return rc;
-    if (int rc = ensure_slots(ctx, 1)) return rc;
-    if (int rc = clear_slots(ctx, 1)) return rc;
+    if (int rc = prepare_sums(ctx, 1)) return rc;
     HIP_CHECK(ctx, gol::launch_hash(ctx->plane[ctx->cur], ctx->pitch, ctx->wwords, ctx->row0, (int32_t)ctx->rows,
-                                    ctx->ilv, ctx->slots, ctx->compute));
-    return read_hashes(ctx, 1, hash_out);
+                                    ctx->ilv, ctx->sums.dev, ctx->compute));
+    return read_sums(ctx, 1, hash_out, nullptr);
 }
 
 int gol_host_alloc(size_t bytes, void** out) {
@@ -548,7 +523,7 @@ int gol_set_tuning(gol_ctx* ctx, int32_t band_rows, int32_t gens_per_pass, int32
 int gol_pass_plan(gol_ctx* ctx, uint32_t generations, int32_t with_hashes, int32_t* depths, int32_t max,
                   int32_t* count) {
     if (!ctx || !count || (max > 0 && !depths)) return set_err(ctx, GOL_EINVAL, "null argument");
-    if (generations > 1024) return set_err(ctx, GOL_EINVAL, "plans cover at most 1024 generations");
+    if (generations > kStepChunk) return set_err(ctx, GOL_EINVAL, "plans cover at most 1024 generations");
     const std::vector<int> plan = plan_passes(ctx, generations, with_hashes != 0);
     for (size_t k = 0; k < plan.size() && (int32_t)k < max; ++k) depths[k] = plan[k];
     *count = (int32_t)plan.size();

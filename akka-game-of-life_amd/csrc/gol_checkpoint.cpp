@@ -43,10 +43,8 @@ int gol_replay(gol_ctx* ctx, uint32_t generations, const uint32_t* above, const 
     const int64_t ext = ctx->rows + 2 * n;
     if (ext > (1 << 30)) return set_err(ctx, GOL_EINVAL, "light cone too deep");
     if (int rc = bind(ctx)) return rc;
-    if (hashes_out) {
-        if (int rc = ensure_slots(ctx, generations)) return rc;
-        if (int rc = clear_slots(ctx, generations)) return rc;
-    }
+    if (hashes_out)
+        if (int rc = prepare_sums(ctx, generations)) return rc;
     const size_t bytes = (size_t)ext * ctx->pitch * sizeof(uint32_t);
     uint32_t* blk[2] = {nullptr, nullptr};
     auto release = [&]() {
@@ -110,7 +108,7 @@ int gol_replay(gol_ctx* ctx, uint32_t generations, const uint32_t* above, const 
         cur ^= 1;
         if (hashes_out) {
             e = gol::launch_hash(blk[cur] + n * pitch, pitch, ctx->wwords, ctx->row0, (int32_t)ctx->rows, ctx->ilv,
-                                 ctx->slots + (size_t)g * gol::kHashGenStride, ctx->compute);
+                                 ctx->sums.dev + (size_t)g * gol::kHashGenStride, ctx->compute);
             if (e != hipSuccess) return fail_hip(e, "light-cone hash");
         }
     }
@@ -119,7 +117,7 @@ int gol_replay(gol_ctx* ctx, uint32_t generations, const uint32_t* above, const 
                        hipMemcpyDeviceToDevice, ctx->compute);
     if (e != hipSuccess) return fail_hip(e, "light-cone result");
     if (hashes_out) {
-        if (int rc = read_hashes(ctx, generations, hashes_out)) {  // synchronises
+        if (int rc = read_sums(ctx, generations, hashes_out, nullptr)) {  // synchronises
             release();
             return rc;
         }

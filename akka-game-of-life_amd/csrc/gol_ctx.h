@@ -14,9 +14,13 @@
 //   gol_schedule.cpp   kernel instance and strip count of a pass, its kernel
 //                      launches (whole shard, interior and boundary rows) and
 //                      pass plan: gathers gol_plan.h's inputs from the context
-//   gol_ring.cpp       the ring schedule: RCCL and loopback halo exchange,
-//                      one_pass (and its active-row branch, gol_set_active_rows,
-//                      gol_active_*), gol_comm_*
+//   gol_ring.cpp       the ring schedule: one_pass, the RCCL halo exchange and
+//                      the RCCL gol_comm_* entry points
+//   gol_loopback.cpp   the in-process loopback ring that stands in for RCCL in
+//                      tests (gol_comm_init_loopback)
+//   gol_active.cpp     the pass of a context stepped whole: one launch, or with
+//                      active-row stepping one per run of live rows
+//                      (gol_set_active_rows, gol_active_*)
 //   gol_group.cpp      in-process shard groups (gol_group_*)
 //   gol_checkpoint.cpp snapshots, checkpoints, restore and light-cone replay
 //   gol_profile.cpp    kernel timing, the in-kernel clock probe, gol_profile_*
@@ -36,6 +40,7 @@
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
+#include <algorithm>
 #include <cstdint>
 #include <map>
 #include <memory>
@@ -46,7 +51,7 @@
 #include "gol_active.h"
 #include "gol_kernels.h"
 
-struct LoopRing;  // gol_ring.cpp
+struct LoopRing;  // gol_loopback.cpp
 
 // In-process shard group: shards in row order, linked into a ring (torus) or
 // a chain (clipped); each shard's comm stream pulls its neighbours' edge rows.
@@ -71,6 +76,52 @@ struct EventPair {
 
 // Clock-probe slots per context (one per profiled launch between folds).
 constexpr uint32_t kClockSlots = 1024;  // 4 KiB each
+
+// Generations a step plans, accumulates and folds at a time (step_chunks): the
+// hash accumulators are allocated for one chunk, 4 MiB.
+constexpr uint32_t kStepChunk = 1024;
+
+// A device buffer that kernels sum into and its owner: the device words, the
+// mapped page-locked words their fold / export kernel leaves the result in
+// (none for a device-only buffer), and how much of the device words is known
+// to be in the reset state, left so by that kernel.  Each owner resets in its
+// own way (a memset, launch_census_reset) and reports a failure with its own
+// code.  `count` and `clean` are in the owner's unit (generations of hash
+// slots, counts, words).
+template <class T>
+struct Accum {
+    T* dev = nullptr;
+    T* host = nullptr;      // coherent: the fold's stores reach host memory without a cache flush
+    T* host_dev = nullptr;  // ... its device address (the fold stores there)
+    size_t count = 0;       // capacity; set only once every buffer exists
+    size_t clean = 0;       // leading units of `dev` known to be in the reset state
+
+    // Forgets the buffers before freeing them, so a failure leaves nothing to
+    // free twice.  The first failing status.
+    hipError_t release() {
+        T* const d = dev;
+        T* const h = host;
+        dev = host = host_dev = nullptr;
+        count = clean = 0;
+        const hipError_t ed = d ? hipFree(d) : hipSuccess;
+        const hipError_t eh = h ? hipHostFree(h) : hipSuccess;
+        return ed != hipSuccess ? ed : eh;
+    }
+    // Holds `n` units afterwards: dev_words device words and host_words mapped
+    // ones (0: device only), none of them clean.  A buffer that is too small
+    // is replaced (nothing may be in flight on it); on failure nothing is held.
+    hipError_t grow(size_t n, size_t dev_words, size_t host_words) {
+        if (n <= count) return hipSuccess;
+        hipError_t e = release();
+        if (e == hipSuccess) e = hipMalloc(&dev, dev_words * sizeof(T));
+        if (e == hipSuccess && host_words)
+            e = hipHostMalloc((void**)&host, host_words * sizeof(T), hipHostMallocMapped | hipHostMallocCoherent);
+        if (e == hipSuccess && host_words) e = hipHostGetDevicePointer((void**)&host_dev, host, 0);
+        if (e == hipSuccess) count = n;
+        else (void)release();
+        return e;
+    }
+};
 
 // The rows of a plane that can hold a live cell: every
 // word of the plane outside `runs` (local rows) is zero, or nothing is known.
@@ -99,12 +150,9 @@ struct gol_ctx {
     uint32_t* halo_top = nullptr;  // RCCL receive buffers (sharded)
     uint32_t* halo_bot = nullptr;
     uint32_t* zero_row = nullptr;
-    unsigned long long* slots = nullptr;  // [gens][kHashSlots * kHashSlotStride]
-    uint32_t slots_gens = 0;
-    uint32_t slots_clean = 0;  // leading generations of `slots` known to be zero (left so by read_hashes)
-    unsigned long long* host_folded = nullptr;      // [2][slots_gens] page-locked, mapped: per-generation hash
-                                                    // sums, then (gol_step_series) populations
-    unsigned long long* host_folded_dev = nullptr;  // ... its device address (fold_kernel stores there)
+    // per-generation sums, in generations: dev [count][kHashGenStride], zero when clean; host [2][count], the
+    // folded hashes and then (gol_step_series) the populations
+    golc::Accum<unsigned long long> sums;
     uint64_t epoch = 0;
     hipStream_t compute = nullptr, comm = nullptr;
     hipStream_t edge = nullptr;  // boundary-row kernels of a sharded pass (concurrent with the interior)
@@ -117,24 +165,16 @@ struct gol_ctx {
     hipEvent_t ev_snap_ready = nullptr, ev_snap_done = nullptr;
     bool snap_pending = false;
     uint64_t snap_epoch = 0;
-    // census and windows (gol_region.cpp), allocated on first use: the staged
-    // window rows this shard owns (packed, ceil(w / 32) words per row), the
-    // census accumulators and the mapped page-locked words their fold lands in
-    uint32_t* region_stage = nullptr;
-    size_t region_stage_words = 0;
-    unsigned long long* census_slots = nullptr;     // kCensusSlots * kCensusSlotStride
-    bool census_clean = false;                      // the slots hold the identity (left so by the fold)
-    unsigned long long* census_host = nullptr;      // kCensusValues, page-locked, mapped
-    unsigned long long* census_host_dev = nullptr;  // ... its device address
-    // density map (gol_density), allocated on first use and grown on demand:
-    // the device grid the kernels count into and the mapped page-locked words
-    // it is exported to before they are added into the caller's buffer
-    uint32_t* density_grid = nullptr;
-    uint32_t* density_host = nullptr;
-    uint32_t* density_host_dev = nullptr;  // ... its device address
-    size_t density_words = 0;
-    bool density_clean = false;            // the grid is all zero (left so by the export)
-    // active-row stepping (gol_active.h, gol_ring.cpp):
+    // census, windows and density map (gol_region.cpp), allocated on first use
+    // and grown on demand: the staged window rows this shard owns (packed,
+    // ceil(w / 32) words per row; device only), the census accumulators
+    // (kCensusSlots * kCensusSlotStride, the identity when clean; host:
+    // kCensusValues) and the grid the density kernels count into (in counts,
+    // zero when clean; exported to the host before it is added to the caller's)
+    golc::Accum<uint32_t> region_stage;
+    golc::Accum<unsigned long long> census;
+    golc::Accum<uint32_t> density;
+    // active-row stepping (gol_active.h, gol_active.cpp):
     // live[p] is kept for plane p by every writer of a plane, mode on or off
     golc::LiveRows live[2];                // gol_create clears both planes: known, no runs
     bool active_on = false;                // gol_set_active_rows
@@ -142,10 +182,7 @@ struct gol_ctx {
     int active_backoff = 0;                // passes between scans while they keep finding the board dense
     int active_wait = 0;                   // ... of them still to go before the next scan
     gol_active_stats active_stats{};
-    uint32_t* active_bits = nullptr;       // the scan's block bitmap (device), one bit per kActiveBlock rows
-    uint32_t* active_host = nullptr;       // ... exported here: page-locked, mapped
-    uint32_t* active_host_dev = nullptr;   // ... its device address
-    bool active_bits_clean = false;        // the device bitmap is all zero (left so by the export)
+    golc::Accum<uint32_t> active_bits;     // the scan's block bitmap, one bit per kActiveBlock rows (in words)
     // RCCL
     ncclComm_t nccl = nullptr;
     int rank = 0, nranks = 1;
@@ -229,17 +266,14 @@ void destroy_impl(gol_ctx* c);
 
 // ---- pass schedule (gol_schedule.cpp) --------------------------------------
 
-int ensure_slots(gol_ctx* ctx, uint32_t gens);
-// Before a hashed chunk: the first `gens` generations' accumulators zero
-// (a memset unless read_hashes left them so); marks them in use.
-int clear_slots(gol_ctx* ctx, uint32_t gens);
+// Before a chunk that sums: accumulators for `gens` generations exist and are
+// zero (a memset unless read_sums left them so); marks them in use.
+int prepare_sums(gol_ctx* ctx, uint32_t gens);
 // After the chunk's passes on the compute stream: its `gens` generations'
-// hashes into out[], folded on the device straight into mapped host memory,
-// the accumulators cleared again; synchronises.
-int read_hashes(gol_ctx* ctx, uint32_t gens, uint64_t* out);
-// The same after a chunk of series passes (PassLaunch::series with kSeriesPop):
-// the hashes and the populations, each into its array unless null.
-int read_series(gol_ctx* ctx, uint32_t gens, uint64_t* hashes_out, uint64_t* populations_out);
+// hashes and populations, each into its array unless null, folded on the
+// device straight into mapped host memory (the populations only if asked
+// for), the accumulators cleared again; synchronises.
+int read_sums(gol_ctx* ctx, uint32_t gens, uint64_t* hashes_out, uint64_t* populations_out);
 int lane_words(const gol_ctx* ctx, int gens);
 // The kernel instance a pass of `gens` generations runs on this context: the
 // one place that derives it (and so a pass's strip width, gol::strip_words).
@@ -260,6 +294,18 @@ struct PlaneGeom {
 // the state hash (gol_step), the population (gol_step_series), or both.
 enum Series { kSeriesHash = 1, kSeriesPop = 2 };
 
+// What a pass accumulates and where: the accumulators of its first generation
+// (null: it sums nothing) and the series it sums into them.
+struct PassSums {
+    unsigned long long* slots = nullptr;
+    int series = 0;  // Series bits
+};
+// ... for a pass that starts `g` generations into the chunk the context's
+// accumulators were prepared for (series 0: a pass that sums nothing).
+inline PassSums pass_sums(const gol_ctx* ctx, int series, uint32_t g) {
+    return series ? PassSums{ctx->sums.dev + (size_t)g * gol::kHashGenStride, series} : PassSums{};
+}
+
 // One launch of a pass: `gens` generations over local row ranges
 // [lo[0], hi[0]) (+ [lo[1], hi[1]) if n == 2).
 struct PassLaunch {
@@ -270,8 +316,7 @@ struct PassLaunch {
     const uint32_t* halo_bot = nullptr;  // (0: one row repeated)
     int64_t halo_stride = 0;
     bool wrap_y = false;                 // unsharded torus: rows wrap inside the plane, no halo read
-    unsigned long long* slots = nullptr;  // hash accumulators of these generations, or null (unhashed)
-    int series = kSeriesHash;             // what a pass with slots accumulates (Series bits)
+    PassSums sums;
     int n = 1;
     int32_t lo[2] = {0, 0}, hi[2] = {0, 0};
     int prof_kind = kProfMain;
@@ -284,14 +329,35 @@ struct PassLaunch {
 // small-board test).
 int strip_count(const gol_ctx* ctx, gol::StepInstance k, bool halo_lanes = false);
 int launch_ranges(gol_ctx* ctx, const PassLaunch& launch);
-int sharded_interior(gol_ctx* ctx, int G, unsigned long long* slots, bool has_up, bool has_down,
-                     int series = kSeriesHash);
-int sharded_boundary(gol_ctx* ctx, int G, unsigned long long* slots, bool has_up, bool has_down,
-                     const hipEvent_t* halo_ready, int nready, int series = kSeriesHash);
-int sharded_pass_kernels(gol_ctx* ctx, int G, unsigned long long* slots, bool has_up, bool has_down,
-                         const hipEvent_t* halo_ready, int nready, int series = kSeriesHash);
+int sharded_interior(gol_ctx* ctx, int G, PassSums sums, bool has_up, bool has_down);
+int sharded_boundary(gol_ctx* ctx, int G, PassSums sums, bool has_up, bool has_down, const hipEvent_t* halo_ready,
+                     int nready);
+int sharded_pass_kernels(gol_ctx* ctx, int G, PassSums sums, bool has_up, bool has_down,
+                         const hipEvent_t* halo_ready, int nready);
 int depth_cap(const gol_ctx* ctx);
 std::vector<int> plan_passes(const gol_ctx* ctx, uint32_t n, bool hashed);
+
+// The one chunk loop of every step: `generations` in chunks of kStepChunk,
+// each planned on `ctx` (any series is planned as a hashed step is, DESIGN.md
+// section 5d).  Per chunk of n generations: prepare(n), then pass(G, g) for
+// each planned depth G, g generations into the chunk, then read(g0, n) for
+// the chunk that began at generation g0.  Not `summed`: passes only.
+template <class Prepare, class Pass, class Read>
+int step_chunks(const gol_ctx* ctx, uint32_t generations, bool summed, Prepare prepare, Pass pass, Read read) {
+    for (uint32_t g0 = 0; g0 < generations; g0 += kStepChunk) {
+        const uint32_t n = std::min(kStepChunk, generations - g0);
+        if (summed)
+            if (int rc = prepare(n)) return rc;
+        uint32_t g = 0;
+        for (const int G : plan_passes(ctx, n, summed)) {
+            if (int rc = pass(G, g)) return rc;
+            g += (uint32_t)G;
+        }
+        if (summed)
+            if (int rc = read(g0, n)) return rc;
+    }
+    return GOL_OK;
+}
 
 // ---- ring schedule (gol_ring.cpp) ------------------------------------------
 
@@ -304,8 +370,19 @@ struct HaloOp {
     int peer;
 };
 
-int one_pass(gol_ctx* ctx, int G, unsigned long long* slots, int series = kSeriesHash);
+int one_pass(gol_ctx* ctx, int G, PassSums sums);
+
+// ---- loopback ring (gol_loopback.cpp) --------------------------------------
+
+int loop_exchange(gol_ctx* ctx, const HaloOp* ops, int n);
+int loop_allreduce(gol_ctx* ctx, uint64_t* values, uint32_t count);
 void loop_leave(gol_ctx* ctx);
+
+// ---- a context stepped whole, active rows (gol_active.cpp) -----------------
+
+// The launches of an unsharded pass (L: everything but the row ranges) and
+// what they make of the live rows of both planes.
+int whole_pass(gol_ctx* ctx, PassLaunch L);
 
 // What the writers of a plane owe the active-row invariant (LiveRows):
 // plane p may now hold anything ...

@@ -32,7 +32,9 @@ int group_fail(gol_group* g, const gol_ctx* s, int rc) {
 //    neighbours' pulls (ev_halo of all three), so its next pass cannot
 //    overwrite rows a neighbour is still reading, and its next pull cannot
 //    overwrite halo rows its boundary kernels still read.
-int group_pass(gol_group* g, int G, const std::vector<unsigned long long*>& slots, int series) {
+// The pass starts `g0` generations into the chunk the shards' accumulators
+// were prepared for (series 0: it sums nothing).
+int group_pass(gol_group* g, int G, int series, uint32_t g0) {
     const int n = (int)g->shards.size();
     for (gol_ctx* s : g->shards) {
         if (int rc = bind(s)) return group_fail(g, s, rc);
@@ -68,8 +70,7 @@ int group_pass(gol_group* g, int G, const std::vector<unsigned long long*>& slot
         if (has_up) ready[nr++] = up->ev_halo;
         if (has_down) ready[nr++] = dn->ev_halo;
         if (int rc = bind(s)) return group_fail(g, s, rc);
-        if (int rc =
-                sharded_pass_kernels(s, G, slots.empty() ? nullptr : slots[k], has_up, has_down, ready, nr, series))
+        if (int rc = sharded_pass_kernels(s, G, pass_sums(s, series, g0), has_up, has_down, ready, nr))
             return group_fail(g, s, rc);
     }
     for (gol_ctx* s : g->shards) {
@@ -184,54 +185,33 @@ int golc::group_step(gol_group* g, uint32_t generations, uint64_t* hashes_out, u
     for (const gol_ctx* s : g->shards)
         if (!s) return GOL_ESTATE;  // g->err names the lost shard
     if (generations == 0) return GOL_OK;
-    const size_t per = (size_t)gol::kHashGenStride;
-    const int n = (int)g->shards.size();
-    constexpr uint32_t kChunk = 1024;
-    std::vector<uint64_t> part, ppart;
-    const bool any = hashes_out || populations_out;
-    const int series = populations_out ? (hashes_out ? kSeriesHash | kSeriesPop : kSeriesPop) : kSeriesHash;
-    for (uint32_t g0 = 0; g0 < generations; g0 += kChunk) {
-        const uint32_t cnt = std::min(kChunk, generations - g0);
-        std::vector<unsigned long long*> base;
-        if (any) {
+    const int series = (hashes_out ? kSeriesHash : 0) | (populations_out ? kSeriesPop : 0);
+    std::vector<uint64_t> part(std::min(generations, kStepChunk)), ppart(part.size());  // one shard's chunk
+    return step_chunks(
+        g->shards[0], generations, series != 0,
+        [&](uint32_t cnt) {
             for (gol_ctx* s : g->shards) {
                 if (int rc = bind(s)) return group_fail(g, s, rc);
-                if (int rc = ensure_slots(s, cnt)) return group_fail(g, s, rc);
-                if (int rc = clear_slots(s, cnt)) return group_fail(g, s, rc);
-                base.push_back(s->slots);
+                if (int rc = prepare_sums(s, cnt)) return group_fail(g, s, rc);
             }
-        }
-        uint32_t done = 0;
-        for (const int G : plan_passes(g->shards[0], cnt, any)) {  // any series: the hashed plan
-            std::vector<unsigned long long*> slots;
-            for (unsigned long long* b : base) slots.push_back(b + done * per);
-            if (int rc = group_pass(g, G, slots, series)) return rc;
-            done += (uint32_t)G;
-        }
-        if (any) {
-            for (uint32_t k = 0; k < cnt; ++k) {
-                if (hashes_out) hashes_out[g0 + k] = 0;
-                if (populations_out) populations_out[g0 + k] = 0;
-            }
-            part.resize(cnt);
-            ppart.resize(cnt);
-            for (int k = 0; k < n; ++k) {
+            return GOL_OK;
+        },
+        [&](int G, uint32_t done) { return group_pass(g, G, series, done); },
+        [&](uint32_t g0, uint32_t cnt) {
+            if (hashes_out) std::fill_n(hashes_out + g0, cnt, 0);
+            if (populations_out) std::fill_n(populations_out + g0, cnt, 0);
+            for (size_t k = 0; k < g->shards.size(); ++k) {
                 gol_ctx* s = g->shards[k];
                 if (int rc = bind(s)) return group_fail(g, s, rc);
-                if (populations_out) {
-                    if (int rc = read_series(s, cnt, part.data(), ppart.data())) return group_fail(g, s, rc);
-                    for (uint32_t j = 0; j < cnt; ++j) populations_out[g0 + j] += ppart[j];
-                } else if (int rc = read_hashes(s, cnt, part.data())) {
+                if (int rc = read_sums(s, cnt, hashes_out ? part.data() : nullptr,
+                                       populations_out ? ppart.data() : nullptr))
                     return group_fail(g, s, rc);
-                }
-                if (hashes_out)
-                    for (uint32_t j = 0; j < cnt; ++j) hashes_out[g0 + j] += part[j];
-                if (partials_out)
-                    std::copy(part.begin(), part.end(), partials_out + (size_t)k * generations + g0);
+                for (uint32_t j = 0; hashes_out && j < cnt; ++j) hashes_out[g0 + j] += part[j];
+                for (uint32_t j = 0; populations_out && j < cnt; ++j) populations_out[g0 + j] += ppart[j];
+                if (partials_out) std::copy_n(part.begin(), cnt, partials_out + k * generations + g0);
             }
-        }
-    }
-    return GOL_OK;
+            return GOL_OK;
+        });
 }
 
 extern "C" {

@@ -65,64 +65,20 @@ int check_window(gol_ctx* ctx, const char* what, int64_t x0, int64_t y0, int64_t
 // The staging buffer holds `words` words.  Nothing is in flight on it between
 // calls: both region calls synchronise before they return.
 int ensure_stage(gol_ctx* ctx, size_t words) {
-    if (words <= ctx->region_stage_words) return GOL_OK;
-    uint32_t* old = ctx->region_stage;
-    ctx->region_stage = nullptr;  // forgotten before it is freed: a failure leaves nothing to free twice
-    ctx->region_stage_words = 0;
-    if (old) HIP_CHECK(ctx, hipFree(old));
-    if (hipMalloc(&ctx->region_stage, words * sizeof(uint32_t)) != hipSuccess) {
-        (void)hipGetLastError();
-        ctx->region_stage = nullptr;
-        return set_err(ctx, GOL_ENOMEM, "hipMalloc of %zu bytes for the window staging buffer failed",
-                       words * sizeof(uint32_t));
-    }
-    ctx->region_stage_words = words;
-    return GOL_OK;
+    if (ctx->region_stage.grow(words, words, 0) == hipSuccess) return GOL_OK;
+    (void)hipGetLastError();
+    return set_err(ctx, GOL_ENOMEM, "hipMalloc of %zu bytes for the window staging buffer failed",
+                   words * sizeof(uint32_t));
 }
 
 // The density grid and the mapped page-locked words it is exported to hold
 // `words` counts.  Nothing is in flight on them between calls: gol_density
 // synchronises before it adds.
 int ensure_density(gol_ctx* ctx, size_t words) {
-    if (words <= ctx->density_words) return GOL_OK;
-    uint32_t* old_grid = ctx->density_grid;
-    uint32_t* old_host = ctx->density_host;
-    ctx->density_grid = ctx->density_host = ctx->density_host_dev = nullptr;  // forgotten before they are freed
-    ctx->density_words = 0;
-    ctx->density_clean = false;
-    if (old_grid) HIP_CHECK(ctx, hipFree(old_grid));
-    if (old_host) HIP_CHECK(ctx, hipHostFree(old_host));
-    // coherent: the export's stores reach host memory without a cache flush
-    if (hipMalloc(&ctx->density_grid, words * sizeof(uint32_t)) != hipSuccess ||
-        hipHostMalloc((void**)&ctx->density_host, words * sizeof(uint32_t),
-                      hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess ||
-        hipHostGetDevicePointer((void**)&ctx->density_host_dev, ctx->density_host, 0) != hipSuccess) {
-        (void)hipGetLastError();
-        if (ctx->density_grid) hip_note(hipFree(ctx->density_grid), "gol_density: hipFree");
-        if (ctx->density_host) hip_note(hipHostFree(ctx->density_host), "gol_density: hipHostFree");
-        ctx->density_grid = ctx->density_host = ctx->density_host_dev = nullptr;
-        return set_err(ctx, GOL_ENOMEM, "allocating %zu bytes for the density map on the device and the host failed",
-                       words * sizeof(uint32_t));
-    }
-    ctx->density_words = words;
-    return GOL_OK;
-}
-
-int ensure_census(gol_ctx* ctx) {
-    if (!ctx->census_slots) {
-        ctx->census_clean = false;
-        HIP_CHECK(ctx, hipMalloc(&ctx->census_slots,
-                                 (size_t)gol::kCensusSlots * gol::kCensusSlotStride * sizeof(unsigned long long)));
-    }
-    if (!ctx->census_host) {
-        // coherent: the fold's stores reach host memory without a cache flush
-        HIP_CHECK(ctx, hipHostMalloc((void**)&ctx->census_host, gol::kCensusValues * sizeof(unsigned long long),
-                                     hipHostMallocMapped | hipHostMallocCoherent));
-        ctx->census_host_dev = nullptr;
-    }
-    if (!ctx->census_host_dev)
-        HIP_CHECK(ctx, hipHostGetDevicePointer((void**)&ctx->census_host_dev, ctx->census_host, 0));
-    return GOL_OK;
+    if (ctx->density.grow(words, words, words) == hipSuccess) return GOL_OK;
+    (void)hipGetLastError();
+    return set_err(ctx, GOL_ENOMEM, "allocating %zu bytes for the density map on the device and the host failed",
+                   words * sizeof(uint32_t));
 }
 
 }  // namespace
@@ -132,15 +88,16 @@ extern "C" {
 int gol_census(gol_ctx* ctx, gol_census_result* out) {
     if (!ctx || !out) return set_err(ctx, GOL_EINVAL, "gol_census: null argument");
     if (int rc = bind(ctx)) return rc;
-    if (int rc = ensure_census(ctx)) return rc;
-    if (!ctx->census_clean) HIP_CHECK(ctx, gol::launch_census_reset(ctx->census_slots, ctx->compute));
-    ctx->census_clean = false;  // in use until the fold has left the identity behind
+    Accum<unsigned long long>& acc = ctx->census;
+    HIP_CHECK(ctx, acc.grow(1, (size_t)gol::kCensusSlots * gol::kCensusSlotStride, gol::kCensusValues));
+    if (!acc.clean) HIP_CHECK(ctx, gol::launch_census_reset(acc.dev, ctx->compute));
+    acc.clean = 0;  // in use until the fold has left the identity behind
     HIP_CHECK(ctx, gol::launch_census(ctx->plane[ctx->cur], ctx->pitch, ctx->wwords, ctx->row0, (int32_t)ctx->rows,
-                                      ctx->ilv, ctx->census_slots, ctx->compute));
-    HIP_CHECK(ctx, gol::launch_census_fold(ctx->census_slots, ctx->census_host_dev, ctx->compute));
+                                      ctx->ilv, acc.dev, ctx->compute));
+    HIP_CHECK(ctx, gol::launch_census_fold(acc.dev, acc.host_dev, ctx->compute));
     HIP_CHECK(ctx, hipStreamSynchronize(ctx->compute));
-    ctx->census_clean = true;
-    const unsigned long long* v = ctx->census_host;
+    acc.clean = 1;
+    const unsigned long long* v = acc.host;
     out->population = v[0];
     out->min_x = (int64_t)v[1];
     out->max_x = (int64_t)v[2];
@@ -162,7 +119,7 @@ int gol_read_region(gol_ctx* ctx, int64_t x0, int64_t y0, int64_t w, int64_t h, 
     if (int rc = ensure_stage(ctx, (size_t)(owned * sw))) return rc;
     // gathered on the compute stream: after every queued pass, straight from
     // the current plane (the pair layout is undone per word, no spare plane)
-    uint32_t* stage = ctx->region_stage;
+    uint32_t* stage = ctx->region_stage.dev;
     for (int k = 0; k < nruns; ++k) {
         const RowRun& r = runs[k];
         HIP_CHECK(ctx, gol::launch_region_gather(ctx->plane[ctx->cur] + r.local_row * ctx->pitch, ctx->pitch,
@@ -193,7 +150,7 @@ int gol_write_region(gol_ctx* ctx, int64_t x0, int64_t y0, int64_t w, int64_t h,
     // copy of a snapshot in flight (gol_snapshot_async copies the board there
     // first).  The epoch stays: neighbours pull this plane's edge rows again
     // at the start of the next pass, after this stream's work.
-    uint32_t* stage = ctx->region_stage;
+    uint32_t* stage = ctx->region_stage.dev;
     for (int k = 0; k < nruns; ++k) {
         const RowRun& r = runs[k];
         HIP_CHECK(ctx, hipMemcpy2DAsync(stage, (size_t)sw * 4, packed + r.win_row * host_pitch_words,
@@ -239,10 +196,10 @@ int gol_density(gol_ctx* ctx, int64_t x0, int64_t y0, int64_t w, int64_t h, int3
     const int64_t piece[2][3] = {{x0, x0 + first, 0}, {0, w - first, first}};
     // On the compute stream: after every queued pass and after the device
     // copy of a snapshot in flight; the board, the epoch and the hash stay.
-    if (!ctx->density_clean)
-        HIP_CHECK(ctx, hipMemsetAsync(ctx->density_grid, 0, ctx->density_words * sizeof(uint32_t), ctx->compute));
-    ctx->density_clean = false;  // in use until the export has left it zero
-    uint32_t* grid = ctx->density_grid;
+    Accum<uint32_t>& acc = ctx->density;
+    if (!acc.clean) HIP_CHECK(ctx, hipMemsetAsync(acc.dev, 0, acc.count * sizeof(uint32_t), ctx->compute));
+    acc.clean = 0;  // in use until the export has left it zero
+    uint32_t* grid = acc.dev;
     for (int k = 0; k < nruns; ++k) {
         const RowRun& r = runs[k];
         const uint32_t* src = ctx->plane[ctx->cur] + r.local_row * ctx->pitch;
@@ -258,10 +215,10 @@ int gol_density(gol_ctx* ctx, int64_t x0, int64_t y0, int64_t w, int64_t h, int3
         }
         grid += map_rows[k] * tw;
     }
-    HIP_CHECK(ctx, gol::launch_density_export(ctx->density_grid, ctx->density_host_dev, (int64_t)words, ctx->compute));
+    HIP_CHECK(ctx, gol::launch_density_export(acc.dev, acc.host_dev, (int64_t)words, ctx->compute));
     HIP_CHECK(ctx, hipStreamSynchronize(ctx->compute));
-    ctx->density_clean = true;
-    const uint32_t* got = ctx->density_host;
+    acc.clean = acc.count;
+    const uint32_t* got = acc.host;
     for (int k = 0; k < nruns; ++k)
         for (int64_t i = 0; i < map_rows[k]; ++i, got += tw) {
             uint32_t* __restrict__ out = counts + (map_row[k] + i) * pitch;

@@ -57,36 +57,17 @@ constexpr int kMaxGensPlannedGeneric = 8;
 
 namespace golc {
 
-int ensure_slots(gol_ctx* ctx, uint32_t gens) {
-    if (gens <= ctx->slots_gens) return GOL_OK;
-    // one allocation for a whole gol_step chunk (1024 generations, 4 MiB):
-    // a hipFree + hipMalloc between two hashed calls would synchronise the
-    // device inside the caller's step
-    gens = std::max<uint32_t>(gens, 1024);
-    // the context forgets both buffers before freeing them, so a failure on
-    // the way leaves nothing to free twice (destroy_impl frees what is set)
-    ctx->slots_gens = 0;
-    ctx->slots_clean = 0;
-    unsigned long long* old_dev = ctx->slots;
-    unsigned long long* old_host = ctx->host_folded;
-    ctx->slots = ctx->host_folded = ctx->host_folded_dev = nullptr;
-    if (old_dev) HIP_CHECK(ctx, hipFree(old_dev));
-    if (old_host) HIP_CHECK(ctx, hipHostFree(old_host));
-    HIP_CHECK(ctx, hipMalloc(&ctx->slots, (size_t)gens * gol::kHashGenStride * sizeof(unsigned long long)));
-    // coherent: fold_kernel's stores reach host memory without a cache flush
-    // twice: the hash sums, then the populations of a series call (read_series)
-    HIP_CHECK(ctx, hipHostMalloc((void**)&ctx->host_folded, 2 * (size_t)gens * sizeof(unsigned long long),
-                                 hipHostMallocMapped | hipHostMallocCoherent));
-    HIP_CHECK(ctx, hipHostGetDevicePointer((void**)&ctx->host_folded_dev, ctx->host_folded, 0));
-    ctx->slots_gens = gens;  // only once every buffer exists
-    return GOL_OK;
-}
-
-int clear_slots(gol_ctx* ctx, uint32_t gens) {
-    const bool clean = ctx->slots_clean >= gens;
-    ctx->slots_clean = 0;  // in use until read_hashes clears them again
+int prepare_sums(gol_ctx* ctx, uint32_t gens) {
+    // one allocation for a whole chunk (kStepChunk generations, 4 MiB): a
+    // hipFree + hipMalloc between two hashed calls would synchronise the
+    // device inside the caller's step.  The mapped words hold the hash sums,
+    // then the populations of a series call (read_sums).
+    const size_t cap = std::max(gens, kStepChunk);
+    HIP_CHECK(ctx, ctx->sums.grow(cap, cap * gol::kHashGenStride, 2 * cap));
+    const bool clean = ctx->sums.clean >= gens;
+    ctx->sums.clean = 0;  // in use until read_sums clears them again
     if (!clean)
-        HIP_CHECK(ctx, hipMemsetAsync(ctx->slots, 0, (size_t)gens * gol::kHashGenStride * sizeof(unsigned long long),
+        HIP_CHECK(ctx, hipMemsetAsync(ctx->sums.dev, 0, (size_t)gens * gol::kHashGenStride * sizeof(unsigned long long),
                                       ctx->compute));
     return GOL_OK;
 }
@@ -95,22 +76,16 @@ int clear_slots(gol_ctx* ctx, uint32_t gens) {
 // board went from 22.0 us (memset + pass + 4 KiB readback) to 20.4 (pass +
 // fold into mapped memory); configs[1]'s hashed 1000 generations from 1.96 to
 // 1.72 ms (8 bytes per generation cross PCIe instead of 4 KiB).
-int read_hashes(gol_ctx* ctx, uint32_t gens, uint64_t* out) {
-    HIP_CHECK(ctx, gol::launch_fold(ctx->slots, gens, ctx->host_folded_dev, ctx->compute));
+int read_sums(gol_ctx* ctx, uint32_t gens, uint64_t* hashes_out, uint64_t* populations_out) {
+    const Accum<unsigned long long>& a = ctx->sums;
+    const size_t pop0 = a.count;  // the populations' half of the mapped words
+    HIP_CHECK(ctx, populations_out
+                       ? gol::launch_fold_series(a.dev, gens, a.host_dev, a.host_dev + pop0, ctx->compute)
+                       : gol::launch_fold(a.dev, gens, a.host_dev, ctx->compute));
     HIP_CHECK(ctx, hipStreamSynchronize(ctx->compute));
-    std::memcpy(out, ctx->host_folded, gens * sizeof(uint64_t));
-    ctx->slots_clean = gens;
-    return GOL_OK;
-}
-
-int read_series(gol_ctx* ctx, uint32_t gens, uint64_t* hashes_out, uint64_t* populations_out) {
-    const size_t pop0 = ctx->slots_gens;  // the populations' half of the mapped words
-    HIP_CHECK(ctx, gol::launch_fold_series(ctx->slots, gens, ctx->host_folded_dev, ctx->host_folded_dev + pop0,
-                                           ctx->compute));
-    HIP_CHECK(ctx, hipStreamSynchronize(ctx->compute));
-    if (hashes_out) std::memcpy(hashes_out, ctx->host_folded, gens * sizeof(uint64_t));
-    if (populations_out) std::memcpy(populations_out, ctx->host_folded + pop0, gens * sizeof(uint64_t));
-    ctx->slots_clean = gens;
+    if (hashes_out) std::memcpy(hashes_out, a.host, gens * sizeof(uint64_t));
+    if (populations_out) std::memcpy(populations_out, a.host + pop0, gens * sizeof(uint64_t));
+    ctx->sums.clean = gens;
     return GOL_OK;
 }
 
@@ -178,9 +153,9 @@ int strip_count(const gol_ctx* ctx, gol::StepInstance k, bool halo_lanes) {
 // profiling events: it is the dominant kernel.
 int launch_ranges(gol_ctx* ctx, const PassLaunch& L) {
     const hipStream_t stream = L.stream ? L.stream : ctx->compute;
-    const bool acc = L.slots != nullptr;
-    const gol::StepInstance k =
-        step_instance(ctx, L.gens, acc && (L.series & kSeriesHash) != 0, acc && (L.series & kSeriesPop) != 0);
+    const bool acc = L.sums.slots != nullptr;
+    const gol::StepInstance k = step_instance(ctx, L.gens, acc && (L.sums.series & kSeriesHash) != 0,
+                                              acc && (L.sums.series & kSeriesPop) != 0);
     const int strips = strip_count(ctx, k);
     const golplan::BandPlan bp = golplan::band_plan(L.n, L.lo, L.hi, strips, L.gens, resident_waves(ctx, k),
                                                     ctx->band_rows, tail_env, gol::kWavesPerWG);
@@ -192,7 +167,7 @@ int launch_ranges(gol_ctx* ctx, const PassLaunch& L) {
     p.halo_bot = L.halo_bot;
     p.halo_stride = L.halo_stride;
     p.wrap_y = L.wrap_y ? 1 : 0;
-    p.hash_slots = L.slots;
+    p.hash_slots = L.sums.slots;
     p.pitch = ctx->pitch;
     p.grow0 = L.geom ? L.geom->grow0 : ctx->row0;
     p.vis_rows = ctx->topology == GOL_TORUS ? ctx->height : ctx->vis_h;
@@ -232,11 +207,10 @@ int launch_ranges(gol_ctx* ctx, const PassLaunch& L) {
 }
 
 // What every launch of a sharded pass shares: the planes, the received halos
-// at the plane's pitch and the hash slots.  A missing neighbour (clipped board
+// at the plane's pitch and the accumulators.  A missing neighbour (clipped board
 // ends) reads dead rows: zero_row holds kMaxGensPerPass of them at the halo
 // pitch.  The caller sets the ranges, the profiling kind and the stream.
-static PassLaunch sharded_launch(gol_ctx* ctx, int G, unsigned long long* slots, bool has_up, bool has_down,
-                                 int series) {
+static PassLaunch sharded_launch(gol_ctx* ctx, int G, PassSums sums, bool has_up, bool has_down) {
     PassLaunch L;
     L.gens = G;
     L.cur = ctx->plane[ctx->cur];
@@ -244,18 +218,17 @@ static PassLaunch sharded_launch(gol_ctx* ctx, int G, unsigned long long* slots,
     L.halo_top = has_up ? ctx->halo_top : ctx->zero_row;
     L.halo_bot = has_down ? ctx->halo_bot : ctx->zero_row;
     L.halo_stride = ctx->pitch;
-    L.slots = slots;
-    L.series = series;
+    L.sums = sums;
     return L;
 }
 
 // The interior rows [G, rows - G) of a sharded pass on the compute stream:
 // they read no halo, so they are enqueued before the exchange (one_pass) and
 // run while it is in flight.  Shards of <= 2G rows have no interior.
-int sharded_interior(gol_ctx* ctx, int G, unsigned long long* slots, bool has_up, bool has_down, int series) {
+int sharded_interior(gol_ctx* ctx, int G, PassSums sums, bool has_up, bool has_down) {
     const int32_t rows = (int32_t)ctx->rows;
     if (rows <= 2 * G) return GOL_OK;
-    PassLaunch L = sharded_launch(ctx, G, slots, has_up, has_down, series);
+    PassLaunch L = sharded_launch(ctx, G, sums, has_up, has_down);
     L.lo[0] = G;
     L.hi[0] = rows - G;
     return launch_ranges(ctx, L);
@@ -267,10 +240,10 @@ int sharded_interior(gol_ctx* ctx, int G, unsigned long long* slots, bool has_up
 // interior one (its waves take the slots the interior's waves free) instead
 // of after it; the compute stream then waits for it, so the next pass, a
 // snapshot or a hash sees the whole plane.
-int sharded_boundary(gol_ctx* ctx, int G, unsigned long long* slots, bool has_up, bool has_down,
-                     const hipEvent_t* halo_ready, int nready, int series) {
+int sharded_boundary(gol_ctx* ctx, int G, PassSums sums, bool has_up, bool has_down, const hipEvent_t* halo_ready,
+                     int nready) {
     const int32_t rows = (int32_t)ctx->rows;
-    PassLaunch L = sharded_launch(ctx, G, slots, has_up, has_down, series);
+    PassLaunch L = sharded_launch(ctx, G, sums, has_up, has_down);
     if (rows > 2 * G) {
         // The exchange events follow this pass's ev_ready, recorded on the
         // compute stream after the previous pass's boundary rows: every
@@ -297,10 +270,10 @@ int sharded_boundary(gol_ctx* ctx, int G, unsigned long long* slots, bool has_up
 // Kernels of one sharded pass whose halos are already on their way (the
 // in-process group): the interior rows, then the boundary rows after
 // `halo_ready`.
-int sharded_pass_kernels(gol_ctx* ctx, int G, unsigned long long* slots, bool has_up, bool has_down,
-                         const hipEvent_t* halo_ready, int nready, int series) {
-    if (int rc = sharded_interior(ctx, G, slots, has_up, has_down, series)) return rc;
-    return sharded_boundary(ctx, G, slots, has_up, has_down, halo_ready, nready, series);
+int sharded_pass_kernels(gol_ctx* ctx, int G, PassSums sums, bool has_up, bool has_down,
+                         const hipEvent_t* halo_ready, int nready) {
+    if (int rc = sharded_interior(ctx, G, sums, has_up, has_down)) return rc;
+    return sharded_boundary(ctx, G, sums, has_up, has_down, halo_ready, nready);
 }
 
 // Deepest pass the context may run.  Every shard of a ring must pick the
