@@ -203,13 +203,13 @@ hipError_t launch_census(const uint32_t* plane, int64_t pitch, int32_t wwords, i
 // identity; `out` may be mapped host memory.
 hipError_t launch_census_fold(unsigned long long* slots, unsigned long long* out, hipStream_t stream);
 
-// Row occupancy (active-row stepping, gol_ring.cpp): bit b of `bits` (`nwords`
+// Row occupancy (active-row stepping, gol_active.cpp): bit b of `bits` (`nwords`
 // words, zero before the first launch that shares them) is set iff block b of
 // kOccupancyBlock rows of the plane holds a non-zero word, for the blocks of
 // local rows [lo, hi), lo a multiple of the block; other bits are left alone.
 // 16-byte loads, as launch_census.  launch_density_export exports the bitmap
 // and leaves it zero.
-constexpr int kOccupancyBlock = 64;  // golactive::kActiveBlock (gol_ring.cpp asserts they agree)
+constexpr int kOccupancyBlock = 64;  // golactive::kActiveBlock (gol_active.cpp asserts they agree)
 hipError_t launch_row_occupancy(const uint32_t* plane, int64_t pitch, int32_t wwords, int32_t lo, int32_t hi,
                                 uint32_t* bits, int32_t nwords, hipStream_t stream);
 

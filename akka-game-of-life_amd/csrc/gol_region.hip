@@ -3,7 +3,7 @@
 // the plane), windows gathered from / scattered into the device layout, and
 // the density map of a window (gol_census, gol_read_region, gol_write_region,
 // gol_density in gol_region.cpp), and the row-occupancy scan of active-row
-// stepping (gol_ring.cpp).
+// stepping (gol_active.cpp).
 #include <algorithm>
 
 #include "gol_kernels.h"
@@ -455,7 +455,7 @@ __global__ void density_export_kernel(unsigned* __restrict__ grid, unsigned* __r
 
 // ---- row occupancy ---------------------------------------------------------------
 // Which blocks of kOccupancyBlock rows hold a non-zero word (active-row
-// stepping, gol_ring.cpp): bit b of `bits` is set iff block b of the plane
+// stepping, gol_active.cpp): bit b of `bits` is set iff block b of the plane
 // does, for the blocks of local rows [lo, hi), lo a multiple of the block.
 // The census's pass -- 16-byte loads, kOccInFlight on their way, a workgroup
 // of 2^lgx chunks times 256 >> lgx rows -- with an OR in place of the counts.

@@ -12,28 +12,29 @@
 // the Infinity Cache) keeping a ring of rows in registers.  Every input word
 // is read from HBM once per pass and every output word written once.
 //
-// Neighbour count: vertical full adder (a + c + b) per column -> two bit
-// planes, DPP wave_shr:1 / wave_shl:1 bring the neighbouring lane's column
-// sums, v_alignbit funnel-shifts them to the x-1 / x+1 columns, and a
-// bit-sliced adder gives the 3x3 box sum T9 (4 bit planes).  B3/S23 is
-// "T9 == 3 | (alive & T9 == 4)"; the generic (birth, survive) path subtracts
-// the centre and evaluates the masks with a v_bfi mux tree.
-//
-// Two kernels:
-//   step_kernel      one generation per pass.  A strip is 64 lanes x VEC
-//                    words; the bits beyond the strip's edges come from one
-//                    extra dword load per row (lane 0: the word left of the
-//                    strip, other lanes: the word right of it) that DPP's
-//                    `old` operand hands to exactly the lanes without a
-//                    source lane.
-//   multistep_kernel G = 2..4 generations per pass (temporal blocking: HBM
-//                    traffic per generation / G).  Lanes 0 and 63 are halo
-//                    lanes holding the neighbouring strips' words; garbage
-//                    enters their outermost bit and moves one bit per
-//                    generation, far from the 32*VEC-bit lane edge, so the
-//                    62 inner lanes are exact.  The intermediate generations
-//                    live only in registers (one 3-row ring per stage) and
-//                    are hashed there; G-row halos come from above/below.
+// Three kernel templates:
+//   step_kernel          G = 1.  A strip is 64 lanes x VEC words; the bits
+//                        beyond its edges come from one extra dword load per
+//                        row that DPP's `old` operand hands to exactly the
+//                        lanes without a source lane.
+//   multistep_hg_kernel  G = 2..12, VEC <= 2 (temporal blocking: HBM traffic
+//                        per generation / G).  Lanes 0 and 63 are halo lanes
+//                        holding the neighbouring strips' words; garbage
+//                        enters their outermost bit and moves one bit per
+//                        generation, far from the 32*VEC-bit lane edge, so the
+//                        62 inner lanes are exact.  The intermediate
+//                        generations live only in registers (a 3-row ring per
+//                        stage); G-row halos come from above / below.
+//   multistep_kernel     G = 2..12, VEC = 4: the same blocking, step_kernel's
+//                        count (hg's three planes per ring row would spill).
+// Neighbour count.  step_kernel and multistep_kernel add each column first
+// (column_sums; DPP and v_alignbit bring the x-1 / x+1 sums: rule_words).
+// multistep_hg_kernel adds each row first (arrive: one 3-sum serves three
+// output rows; rule_hg) and on B3/S23 tori -- the headline -- shares each
+// even/odd row pair's middle sum as well (rule_b3s23_pair).
+// Instances (kernel_one): kBuilt says which exist; (VEC 2, G 10, B3/S23 torus,
+// pair layout) also has a whole-row form (WR); the last template argument KIND
+// is the plane's interleave plus kKindSeries for the population-series kernels.
 #pragma once
 #include <type_traits>
 #include <utility>
@@ -223,6 +224,14 @@ __device__ __forceinline__ WaveTile wave_tile(const StepParams& p, int wave) {
     return {range, w % p.strips, w / p.strips};
 }
 
+// The output rows [r_begin, r_end) of band bandi < p.nbands[rg] of range rg.
+__device__ __forceinline__ void band_rows(const StepParams& p, int rg, int bandi, int& r_begin, int& r_end,
+                                          int& nrows) {
+    r_begin = p.row_lo[rg] + bandi * p.band[rg];
+    r_end = min(r_begin + p.band[rg], p.row_hi[rg]);
+    nrows = r_end - r_begin;
+}
+
 // Local row pointer for r in [-G, rows + G).  Wave-uniform and built from
 // selects rather than branches: it runs once per stream row inside the
 // unrolled loops.  Only tori shorter than a pass's halo (rows < G) take the
@@ -249,6 +258,42 @@ __device__ __forceinline__ bool row_visible(const StepParams& p, int r) {
         return true;
     }
 }
+
+// A lane's place in the row (multi-generation kernels; halo lanes may lie
+// outside it): the column it loads and stores, wrapped or clamped into the
+// row, and -- CLIPPED -- the masks of its visible and of its board columns.
+template <int VEC, bool CLIPPED>
+__device__ __forceinline__ void lane_cols(const StepParams& p, int col, int& lcol, uint32_t (&cmask)[VEC],
+                                          uint32_t (&omask)[VEC]) {
+    bool incol;
+    if (p.wrap_x) {
+        lcol = col % p.wwords;
+        if (lcol < 0) lcol += p.wwords;
+        incol = true;
+    } else {
+        incol = col >= 0 && col < p.wwords;
+        lcol = incol ? col : 0;
+    }
+#pragma unroll
+    for (int j = 0; j < VEC; ++j) {
+        cmask[j] = CLIPPED ? (incol ? col_mask(p.vis_cols, col + j) : 0u) : 0xFFFFFFFFu;
+        omask[j] = CLIPPED ? (incol ? col_mask(p.width, col + j) : 0u) : 0xFFFFFFFFu;
+    }
+}
+
+// A multi-generation band's stream rows m = 0 .. nrows + 2G - 1: local board
+// rows r_begin - G .. r_end + G - 1, bottom-up in odd bands, for every stage.
+template <int VEC, int G, bool CLIPPED>
+struct RowStream {
+    const StepParams& p;
+    const bool& up;
+    const int &r_begin, &r_end, &lcol;
+    __device__ __forceinline__ int brow(int m) const { return up ? r_end - 1 + G - m : r_begin - G + m; }
+    __device__ __forceinline__ bool vis(int m) const { return row_visible<CLIPPED>(p, brow(m)); }
+    __device__ __forceinline__ void load(int m, Words<VEC>& d) const {
+        load_words<VEC>(row_ptr(p, brow(m), G), lcol, d);
+    }
+};
 
 // v_bitop3_b32 truth tables: imm = f(S0 = 0xF0, S1 = 0xCC, S2 = 0xAA).
 constexpr uint32_t kXor3 = 0x96;         // a ^ b ^ c
@@ -386,6 +431,33 @@ __device__ __forceinline__ void neighbours(const T (&v)[VEC], T l, T r, int j, T
     }
 }
 
+// out = the rule from the count n = nb0 + 2 (pp + c0) + 4 qq of rule_words
+// or rule_hg and the centre `al`.  Generic rules: leaf k of a v_bfi mux tree
+// over n's bits is "survive has k" where the centre is alive, else "birth has
+// k".  A macro on purpose: as a function (by value, by reference, with an
+// out-parameter, the mux tree alone) it moved the schedule of the generic
+// kernels, and step_kernel<2,0,1,0,1> and two more crossed an occupancy step
+// (73 -> 71 VGPRs).  Expanded in place every kernel keeps its code.
+#define GOL_RULE_FROM_COUNT(out, LIFE, p, nb0, c0, pp, qq, al)                              \
+    do {                                                                                    \
+        if constexpr (LIFE) {                                                               \
+            const uint32_t x_ = GOL_BITOP3(qq, pp, c0, kNotAXorBC);                         \
+            (out) = GOL_BITOP3(x_, nb0, al, kAAndBOrC);                                     \
+        } else {                                                                            \
+            const uint32_t n1b_ = (pp) ^ (c0), k_ = (pp) & (c0), n2b_ = (qq) ^ k_, n3b_ = (qq) & k_; \
+            uint32_t L_[9];                                                                 \
+            _Pragma("unroll") for (int q_ = 0; q_ < 9; ++q_) {                              \
+                const uint32_t sm_ = (((p).survive >> q_) & 1u) ? 0xFFFFFFFFu : 0u;         \
+                const uint32_t bm_ = (((p).birth >> q_) & 1u) ? 0xFFFFFFFFu : 0u;           \
+                L_[q_] = bfi(al, sm_, bm_);                                                 \
+            }                                                                               \
+            const uint32_t m01_ = bfi(nb0, L_[1], L_[0]), m23_ = bfi(nb0, L_[3], L_[2]);    \
+            const uint32_t m45_ = bfi(nb0, L_[5], L_[4]), m67_ = bfi(nb0, L_[7], L_[6]);    \
+            const uint32_t m03_ = bfi(n1b_, m23_, m01_), m47_ = bfi(n1b_, m67_, m45_);      \
+            (out) = bfi(n3b_, L_[8], bfi(n2b_, m47_, m03_));                                \
+        }                                                                                   \
+    } while (0)
+
 template <int VEC, bool LIFE, int ILV, bool CLIPPED>
 __device__ __forceinline__ void rule_words(const StepParams& p, const uint32_t (&v0)[VEC],
                                            const uint32_t (&v1)[VEC], const uint32_t (&p0)[VEC],
@@ -408,26 +480,7 @@ __device__ __forceinline__ void rule_words(const StepParams& p, const uint32_t (
         const uint32_t pp = GOL_BITOP3(w1, e1, p1[j], kXor3);
         const uint32_t qq = GOL_BITOP3(w1, e1, p1[j], kMaj);
         const uint32_t al = alive.w[j];
-        if constexpr (LIFE) {
-            const uint32_t x = GOL_BITOP3(qq, pp, c0, kNotAXorBC);
-            out.w[j] = GOL_BITOP3(x, nb0, al, kAAndBOrC);
-        } else {
-            const uint32_t n1b = pp ^ c0, k = pp & c0;
-            const uint32_t n2b = qq ^ k, n3b = qq & k;
-            const uint32_t n0b = nb0;
-            uint32_t L[9];
-#pragma unroll
-            for (int k = 0; k < 9; ++k) {
-                const uint32_t sm = ((p.survive >> k) & 1u) ? 0xFFFFFFFFu : 0u;
-                const uint32_t bm = ((p.birth >> k) & 1u) ? 0xFFFFFFFFu : 0u;
-                L[k] = bfi(al, sm, bm);
-            }
-            const uint32_t m01 = bfi(n0b, L[1], L[0]), m23 = bfi(n0b, L[3], L[2]);
-            const uint32_t m45 = bfi(n0b, L[5], L[4]), m67 = bfi(n0b, L[7], L[6]);
-            const uint32_t m03 = bfi(n1b, m23, m01), m47 = bfi(n1b, m67, m45);
-            const uint32_t m07 = bfi(n2b, m47, m03);
-            out.w[j] = bfi(n3b, L[8], m07);
-        }
+        GOL_RULE_FROM_COUNT(out.w[j], LIFE, p, nb0, c0, pp, qq, al);
     }
 }
 
@@ -544,6 +597,9 @@ __device__ __forceinline__ void hash_flush(unsigned long long acc, unsigned long
     }
 }
 
+// (pop_flush_gens is this routine on u32.  One flush_gens<T, G> behind both --
+// slot word as argument or template argument, LDS array inside or handed in --
+// moved the hashed series multistep_hg_kernel<2, 8..9, B3/S23>: kept apart.)
 // All G generations of a multi-generation pass at once: the G wave reductions
 // interleaved, one barrier, and workgroup thread s sums and adds generation
 // s (hash_flush once per generation paid 2G barriers per workgroup: on small
@@ -612,6 +668,14 @@ __device__ __forceinline__ void pop_flush_gens(uint32_t (&cnt)[G], unsigned long
     }
 }
 
+template <int VEC, int N>
+__device__ __forceinline__ void zero_ring(Words<VEC> (&ring)[N]) {
+#pragma unroll
+    for (int k = 0; k < N; ++k)
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) ring[k].w[j] = 0u;
+}
+
 // --------------------------------------------------------------------------
 // One generation per pass.
 // --------------------------------------------------------------------------
@@ -642,6 +706,8 @@ template <int VEC, bool LIFE, bool HASH, bool CLIPPED, int KIND>
 __global__ __launch_bounds__(kWaveLanes* kWavesPerWG) void step_kernel(const StepParams p) {
     constexpr int ILV = kind_ilv(KIND);
     constexpr bool POP = kind_pop(KIND);
+    // These five lines open all three kernels.  One helper (a struct returned, or
+    // out-parameters) drops an s_ashr_i32 from every kernel: tried, kept apart.
     const int lane = threadIdx.x & (kWaveLanes - 1);
     const int wave_in_wg = __builtin_amdgcn_readfirstlane(threadIdx.x / kWaveLanes);
     const WaveTile tile = wave_tile(p, xcd_block(blockIdx.x, gridDim.x, p.xcd_chunk) * kWavesPerWG + wave_in_wg);
@@ -654,9 +720,8 @@ __global__ __launch_bounds__(kWaveLanes* kWavesPerWG) void step_kernel(const Ste
         HashAcc<VEC> hacc;
         hash_clear(hacc);
         uint32_t pacc = 0u;
-        const int r_begin = p.row_lo[rg] + bandi * p.band[rg];
-        const int r_end = min(r_begin + p.band[rg], p.row_hi[rg]);
-        const int nrows = r_end - r_begin;
+        int r_begin, r_end, nrows;
+        band_rows(p, rg, bandi, r_begin, r_end, nrows);
         const int s0 = strip * (kWaveLanes * VEC);
         const int nact = min(kWaveLanes, (p.wwords - s0) / VEC);
         const int col = s0 + lane * VEC;
@@ -823,58 +888,35 @@ __global__ __launch_bounds__(kWaveLanes* kWavesPerWG) void multistep_kernel(cons
     }
 
     if (bandi < p.nbands[rg]) {
-        const int r_begin = p.row_lo[rg] + bandi * p.band[rg];
-        const int r_end = min(r_begin + p.band[rg], p.row_hi[rg]);
-        const int nrows = r_end - r_begin;
+        int r_begin, r_end, nrows;
+        band_rows(p, rg, bandi, r_begin, r_end, nrows);
         const int n_in = nrows + 2 * G;  // stream rows r_begin-G .. r_end+G-1
         const int s0 = strip * kOut;
         const int nout = min(kOut, p.wwords - s0);
         const int col = s0 + (lane - 1) * VEC;  // lane 0: the strip's left halo
         const bool owns = lane >= 1 && (lane - 1) * VEC < nout;
         int lcol;
-        bool incol;
-        if (p.wrap_x) {
-            lcol = col % p.wwords;
-            if (lcol < 0) lcol += p.wwords;
-            incol = true;
-        } else {
-            incol = col >= 0 && col < p.wwords;
-            lcol = incol ? col : 0;
-        }
         uint32_t cmask[VEC], omask[VEC];
-#pragma unroll
-        for (int j = 0; j < VEC; ++j) {
-            cmask[j] = CLIPPED ? (incol ? col_mask(p.vis_cols, col + j) : 0u) : 0xFFFFFFFFu;
-            omask[j] = CLIPPED ? (incol ? col_mask(p.width, col + j) : 0u) : 0xFFFFFFFFu;
-        }
+        lane_cols<VEC, CLIPPED>(p, col, lcol, cmask, omask);
         const bool odd_lane = (col & 1) != 0;
         HashAcc<VEC> hacc[G];
 #pragma unroll
         for (int s = 0; s < G; ++s) hash_clear(hacc[s]);
         const bool up = (bandi & 1) != 0;
-        // stream row m <-> local board row (the same for every stage)
-        auto brow = [&](int m) -> int { return up ? r_end - 1 + G - m : r_begin - G + m; };
-        auto vis = [&](int m) -> bool { return row_visible<CLIPPED>(p, brow(m)); };
+        const RowStream<VEC, G, CLIPPED> rows{p, up, r_begin, r_end, lcol};
 
         Words<VEC> in[kMRing];
         Words<VEC> st[G - 1][3];  // stage s (1..G-1) rows, slot = stream row % 3
+        zero_ring(in);
 #pragma unroll
-        for (int k = 0; k < kMRing; ++k)
-#pragma unroll
-            for (int j = 0; j < VEC; ++j) in[k].w[j] = 0u;
-#pragma unroll
-        for (int s = 0; s < G - 1; ++s)
-#pragma unroll
-            for (int k = 0; k < 3; ++k)
-#pragma unroll
-                for (int j = 0; j < VEC; ++j) st[s][k].w[j] = 0u;
+        for (int s = 0; s < G - 1; ++s) zero_ring(st[s]);
 
-        auto load_m = [&](int m, Words<VEC>& d) { load_words<VEC>(row_ptr(p, brow(m), G), lcol, d); };
         // one stencil application: rows above/centre/below -> out
         auto apply = [&](const Words<VEC>& A, const Words<VEC>& C, const Words<VEC>& B, int mc,
                          Words<VEC>& o) {
             uint32_t v0[VEC], v1[VEC], p0[VEC], p1[VEC];
-            column_sums<VEC, CLIPPED>(A, C, B, vis(mc - 1), vis(mc), vis(mc + 1), cmask, v0, v1, p0, p1);
+            column_sums<VEC, CLIPPED>(A, C, B, rows.vis(mc - 1), rows.vis(mc), rows.vis(mc + 1), cmask, v0, v1, p0,
+                                      p1);
             // halo lanes 0 / 63 read zeros beyond their outer edge (bound_ctrl)
             const uint32_t m0 = dpp_shr1_zero(v0[VEC - 1]);
             const uint32_t m1 = dpp_shr1_zero(v1[VEC - 1]);
@@ -890,7 +932,7 @@ __global__ __launch_bounds__(kWaveLanes* kWavesPerWG) void multistep_kernel(cons
         // Stream row q (slot u = q % kMRing): prefetch row q + kMPF, stage s
         // produces stream row q - s.
         auto row_step = [&](const int q, const int u) {
-            load_m(min(q + kMPF, n_in - 1), in[(u + kMPF) % kMRing]);
+            rows.load(min(q + kMPF, n_in - 1), in[(u + kMPF) % kMRing]);
             // stage 1: stream row q-1 from input rows q-2, q-1, q
             Words<VEC> o;
             apply(in[(u + kMRing - 2) % kMRing], in[(u + kMRing - 1) % kMRing], in[u], q - 1, o);
@@ -898,10 +940,12 @@ __global__ __launch_bounds__(kWaveLanes* kWavesPerWG) void multistep_kernel(cons
             for (int s = 1; s <= G; ++s) {
                 const int m = q - s;  // stream row produced by stage s
                 const bool own_row = m >= G && m < n_in - G;
+                // "hash, then count, if own_row" stands in both branches: one helper,
+                // called after, before or in them, moved the B3/S23 instances' code.
                 if (s < G) {
                     st[s - 1][((u - s) % 3 + 3) % 3] = o;
                     if constexpr (HASH) {
-                        if (own_row) hash_row<VEC, ILV>(p.grow0 + brow(m), o, odd_lane, hacc[s - 1]);
+                        if (own_row) hash_row<VEC, ILV>(p.grow0 + rows.brow(m), o, odd_lane, hacc[s - 1]);
                     }
                     if constexpr (POP) {
                         if (own_row) pcnt[s - 1] = pop_row<VEC>(o, pcnt[s - 1]);
@@ -910,7 +954,7 @@ __global__ __launch_bounds__(kWaveLanes* kWavesPerWG) void multistep_kernel(cons
                     apply(st[s - 1][((u - s - 2) % 3 + 3) % 3], st[s - 1][((u - s - 1) % 3 + 3) % 3],
                           st[s - 1][((u - s) % 3 + 3) % 3], m - 1, o);
                 } else {
-                    const int r = brow(m);
+                    const int r = rows.brow(m);
                     store_row<VEC>(p.nxt + (int64_t)r * p.pitch, own_row, p.wwords * 4, lcol, owns, o);
                     if constexpr (HASH) {
                         if (own_row) hash_row<VEC, ILV>(p.grow0 + r, o, odd_lane, hacc[G - 1]);
@@ -923,7 +967,7 @@ __global__ __launch_bounds__(kWaveLanes* kWavesPerWG) void multistep_kernel(cons
         };
 
 #pragma unroll
-        for (int t = 0; t < kMPF; ++t) load_m(min(t, n_in - 1), in[t]);
+        for (int t = 0; t < kMPF; ++t) rows.load(min(t, n_in - 1), in[t]);
         for (int q0 = 0; q0 < n_in; q0 += kMRing) {
 #pragma unroll
             for (int u = 0; u < kMRing; ++u) row_step(q0 + u, u);
@@ -1009,25 +1053,7 @@ __device__ __forceinline__ void rule_hg(const StepParams& p, const HRow<VEC, CLI
         const uint32_t qq = GOL_BITOP3(A.h1[j], B.h1[j], g1, kMaj);
         const uint32_t al = CLIPPED ? C.a[j] : C.r[j];
         uint32_t res;
-        if constexpr (LIFE) {
-            const uint32_t x = GOL_BITOP3(qq, pp, c0, kNotAXorBC);
-            res = GOL_BITOP3(x, nb0, al, kAAndBOrC);
-        } else {
-            const uint32_t n1b = pp ^ c0, k = pp & c0;
-            const uint32_t n2b = qq ^ k, n3b = qq & k;
-            uint32_t L[9];
-#pragma unroll
-            for (int q = 0; q < 9; ++q) {
-                const uint32_t sm = ((p.survive >> q) & 1u) ? 0xFFFFFFFFu : 0u;
-                const uint32_t bm = ((p.birth >> q) & 1u) ? 0xFFFFFFFFu : 0u;
-                L[q] = bfi(al, sm, bm);
-            }
-            const uint32_t m01 = bfi(nb0, L[1], L[0]), m23 = bfi(nb0, L[3], L[2]);
-            const uint32_t m45 = bfi(nb0, L[5], L[4]), m67 = bfi(nb0, L[7], L[6]);
-            const uint32_t m03 = bfi(n1b, m23, m01), m47 = bfi(n1b, m67, m45);
-            const uint32_t m07 = bfi(n2b, m47, m03);
-            res = bfi(n3b, L[8], m07);
-        }
+        GOL_RULE_FROM_COUNT(res, LIFE, p, nb0, c0, pp, qq, al);
         out.w[j] = CLIPPED ? (res & omask[j]) : res;
     }
 }
@@ -1068,9 +1094,8 @@ __global__ __launch_bounds__(kWaveLanes* kWavesPerWG) void multistep_hg_kernel(c
     for (int s = 0; s < G; ++s) pcnt[s] = 0u;
 
     if (bandi < p.nbands[rg]) {
-        const int r_begin = p.row_lo[rg] + bandi * p.band[rg];
-        const int r_end = min(r_begin + p.band[rg], p.row_hi[rg]);
-        const int nrows = r_end - r_begin;
+        int r_begin, r_end, nrows;
+        band_rows(p, rg, bandi, r_begin, r_end, nrows);
         const int n_in = nrows + 2 * G;
         const int s0 = strip * kOut;
         const int nout = min(kOut, p.wwords - s0);
@@ -1088,21 +1113,8 @@ __global__ __launch_bounds__(kWaveLanes* kWavesPerWG) void multistep_hg_kernel(c
             if (lane > (nout + VEC - 1) / VEC + 1) return;
         }
         int lcol;
-        bool incol;
-        if (p.wrap_x) {
-            lcol = col % p.wwords;
-            if (lcol < 0) lcol += p.wwords;
-            incol = true;
-        } else {
-            incol = col >= 0 && col < p.wwords;
-            lcol = incol ? col : 0;
-        }
         uint32_t cmask[VEC], omask[VEC];
-#pragma unroll
-        for (int j = 0; j < VEC; ++j) {
-            cmask[j] = CLIPPED ? (incol ? col_mask(p.vis_cols, col + j) : 0u) : 0xFFFFFFFFu;
-            omask[j] = CLIPPED ? (incol ? col_mask(p.width, col + j) : 0u) : 0xFFFFFFFFu;
-        }
+        lane_cols<VEC, CLIPPED>(p, col, lcol, cmask, omask);
         const bool odd_lane = (col & 1) != 0;
         constexpr int kNP = HashAcc<VEC>::kGroups;
         // this lane's LDS sums: generation s, pair k at hsum[(s * kNP + k) * kWaveLanes]
@@ -1118,8 +1130,7 @@ __global__ __launch_bounds__(kWaveLanes* kWavesPerWG) void multistep_hg_kernel(c
             for (int k = 0; k < G; ++k) psum[k * kWaveLanes] = 0u;
         }
         const bool up = (bandi & 1) != 0;
-        auto brow = [&](int m) -> int { return up ? r_end - 1 + G - m : r_begin - G + m; };
-        auto vis = [&](int m) -> bool { return row_visible<CLIPPED>(p, brow(m)); };
+        const RowStream<VEC, G, CLIPPED> rows{p, up, r_begin, r_end, lcol};
 
         Words<VEC> in[kMRing];
         HRow<VEC, CLIPPED> hr[G][3];  // ring s: arrivals of stage-s rows (stage 0 = input), slot = row % 3
@@ -1128,10 +1139,7 @@ __global__ __launch_bounds__(kWaveLanes* kWavesPerWG) void multistep_hg_kernel(c
         for (int s = 0; s < (kPairRows<VEC, LIFE, CLIPPED> ? G : 1); ++s)
 #pragma unroll
             for (int j = 0; j < VEC; ++j) pst[s].p0[j] = pst[s].p1[j] = pst[s].p2[j] = 0u;
-#pragma unroll
-        for (int k = 0; k < kMRing; ++k)
-#pragma unroll
-            for (int j = 0; j < VEC; ++j) in[k].w[j] = 0u;
+        zero_ring(in);
 #pragma unroll
         for (int s = 0; s < G; ++s)
 #pragma unroll
@@ -1141,8 +1149,6 @@ __global__ __launch_bounds__(kWaveLanes* kWavesPerWG) void multistep_hg_kernel(c
                     hr[s][k].h0[j] = hr[s][k].h1[j] = hr[s][k].r[j] = 0u;
                     if constexpr (CLIPPED) hr[s][k].a[j] = 0u;
                 }
-
-        auto load_m = [&](int m, Words<VEC>& d) { load_words<VEC>(row_ptr(p, brow(m), G), lcol, d); };
 
         // Hash row keys: stage s at stream row q hashes stream row q - s, so a
         // shift register holds the keys of stream rows q .. q - G, 0 for rows
@@ -1159,7 +1165,7 @@ __global__ __launch_bounds__(kWaveLanes* kWavesPerWG) void multistep_hg_kernel(c
         // hashed or read by a valid row), so the pipeline fill -- the first
         // kFill rows, q known at compile time -- skips those stage steps.
         auto row_step = [&](const int q, const int u, const bool fill) __attribute__((always_inline)) {
-            load_m(min(q + kHgPF, n_in - 1), in[(u + kHgPF) % kMRing]);
+            rows.load(min(q + kHgPF, n_in - 1), in[(u + kHgPF) % kMRing]);
             if constexpr (HASH) {
 #pragma unroll
                 for (int k = G; k >= 1; --k) {
@@ -1167,11 +1173,11 @@ __global__ __launch_bounds__(kWaveLanes* kWavesPerWG) void multistep_hg_kernel(c
                     kao[k] = kao[k - 1];
                 }
                 const bool own_q = q >= G && q < n_in - G;
-                const uint32_t ae = hash_row_key(p.grow0 + brow(q));
+                const uint32_t ae = hash_row_key(p.grow0 + rows.brow(q));
                 kae[0] = own_q ? ae : 0u;
                 kao[0] = own_q ? ae + kHashOddAdd : 0u;
             }
-            arrive<VEC, CLIPPED, ILV, WR>(in[u], vis(q), cmask, hr[0][u % 3]);
+            arrive<VEC, CLIPPED, ILV, WR>(in[u], rows.vis(q), cmask, hr[0][u % 3]);
 #pragma unroll
             for (int s = 1; s <= G; ++s) {
                 // stages s.. have no valid row yet; a paired stage also runs the
@@ -1219,16 +1225,16 @@ __global__ __launch_bounds__(kWaveLanes* kWavesPerWG) void multistep_hg_kernel(c
                     }
                 }
                 if (s < G) {
-                    arrive<VEC, CLIPPED, ILV, WR>(o, vis(m), cmask, hr[s][((u - s) % 3 + 3) % 3]);
+                    arrive<VEC, CLIPPED, ILV, WR>(o, rows.vis(m), cmask, hr[s][((u - s) % 3 + 3) % 3]);
                 } else {
-                    const int r = brow(m);
+                    const int r = rows.brow(m);
                     store_row<VEC>(p.nxt + (int64_t)r * p.pitch, own_row, p.wwords * 4, lcol, owns, o);
                 }
             }
         };
 
 #pragma unroll
-        for (int t = 0; t < kHgPF; ++t) load_m(min(t, n_in - 1), in[t]);
+        for (int t = 0; t < kHgPF; ++t) rows.load(min(t, n_in - 1), in[t]);
         constexpr int kFill = (2 * G + kMRing - 1) / kMRing * kMRing;  // whole ring turns
         // The peeled fill is one long straight-line block; only the B3/S23
         // instances keep their rings in registers through it (the generic-rule
@@ -1299,7 +1305,6 @@ StepKernel kernel_one(bool whole_row) {
         return multistep_kernel<VEC, G, LIFE, HASH, CLIPPED, KIND>;
     }
 }
-
 
 // The instances a launch can select: clipped boards (generic rule, row-major
 // words), tori (B3/S23 fast path or generic rule) in row-major or pair layout

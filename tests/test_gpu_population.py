@@ -148,17 +148,14 @@ def clipped_reference(W, H, gens, seed):
     return (board,) + reference(board, W, gens, O.REF_CLIPPED, O.LIFE)
 
 
-@pytest.mark.parametrize("with_hashes", FAMILIES, ids=FAMILY_IDS)
-@pytest.mark.parametrize("gpp", [1, 2, 5, 8])
-@pytest.mark.parametrize("W", [7, 100, 32 * 62 + 5, 32 * 300 + 17])
-def test_clipped_boards(gpu, W, gpp, with_hashes):
+def check_clipped(W, gpp, with_hashes, lane_words=0):
     """A half-full board, so the sink row and column hold live cells: they are
     stored cells and count, as in the census."""
     H, gens = 23, 2 * gpp + 1
     board, final, hashes, pops = clipped_reference(W, H, gens, W * 3 + gpp)
     assert popcount(board[H - 1]) > 0 and O.unpack(board, W)[:, W - 1].any()  # live sink cells to start from
     with engine(W, H, topology="ref-clipped") as e:
-        e.set_tuning(gens_per_pass=gpp)
+        e.set_tuning(gens_per_pass=gpp, words_per_lane=lane_words)
         check_engine(e, board, W, gens, with_hashes, (final, hashes, pops))
         assert e.census()["population"] == int(pops[-1])
         # generation by generation, the series is the census of that epoch
@@ -166,6 +163,24 @@ def test_clipped_boards(gpu, W, gpp, with_hashes):
         for g in range(3):
             _, p = step_series(e, 1, with_hashes)
             assert int(p[0]) == e.census()["population"] == int(pops[g])
+
+
+@pytest.mark.parametrize("with_hashes", FAMILIES, ids=FAMILY_IDS)
+@pytest.mark.parametrize("gpp", [1, 2, 5, 8])
+@pytest.mark.parametrize("W", [7, 100, 32 * 62 + 5, 32 * 300 + 17])
+def test_clipped_boards(gpu, W, gpp, with_hashes):
+    check_clipped(W, gpp, with_hashes)
+
+
+@pytest.mark.parametrize("with_hashes", FAMILIES, ids=FAMILY_IDS)
+@pytest.mark.parametrize("gpp", [2, 7])  # 7: the deepest clipped 16-byte-lane instance built
+@pytest.mark.parametrize("W", [32 * 11 + 5, 32 * 303 + 17])
+def test_clipped_boards_sixteen_byte_lanes(gpu, W, gpp, with_hashes):
+    # The vertical-first multi-generation kernel's series instances on a clipped
+    # board.  A row of 16-byte lanes is a multiple of 4 words (gol_set_tuning
+    # refuses others), so: 12 words -- one strip, 3 of its 62 lanes, a partial
+    # last word -- and 304 words -- two strips (248 + 56), a partial last word.
+    check_clipped(W, gpp, with_hashes, lane_words=4)
 
 
 @pytest.mark.parametrize("with_hashes", FAMILIES, ids=FAMILY_IDS)
