@@ -137,13 +137,10 @@ void destroy_impl(gol_ctx* c) {
         if (r != ncclSuccess) fprintf(stderr, "libgol: destroy: ncclCommDestroy: %s\n", ncclGetErrorString(r));
         c->nccl = nullptr;
     }
-    for (auto& e : c->evs) {
-        if (e.start) hip_note(hipEventDestroy(e.start), "destroy: hipEventDestroy");
-        if (e.stop) hip_note(hipEventDestroy(e.stop), "destroy: hipEventDestroy");
-    }
+    c->profile.destroy_events();
     for (hipEvent_t ev : {c->ev_ready, c->ev_halo, c->ev_edge, c->ev_snap_ready, c->ev_snap_done})
         if (ev) hip_note(hipEventDestroy(ev), "destroy: hipEventDestroy");
-    for (void* p : {(void*)c->snap, (void*)c->clk_buf, (void*)c->plane[0], (void*)c->plane[1], (void*)c->halo_top,
+    for (void* p : {(void*)c->snap, (void*)c->plane[0], (void*)c->plane[1], (void*)c->halo_top,
                     (void*)c->halo_bot, (void*)c->zero_row})
         if (p) hip_note(hipFree(p), "destroy: hipFree");
     hip_note(c->sums.release(), "destroy: hash accumulators");
@@ -151,6 +148,7 @@ void destroy_impl(gol_ctx* c) {
     hip_note(c->census.release(), "destroy: census accumulators");
     hip_note(c->density.release(), "destroy: density map");
     hip_note(c->active_bits.release(), "destroy: active-row bitmap");
+    hip_note(c->profile.clk.release(), "destroy: clock-probe buffer");
     for (hipStream_t st : {c->compute, c->comm, c->edge, c->xfer})
         if (st) hip_note(hipStreamDestroy(st), "destroy: hipStreamDestroy");
     delete c;

@@ -23,7 +23,10 @@
 //                      (gol_set_active_rows, gol_active_*)
 //   gol_group.cpp      in-process shard groups (gol_group_*)
 //   gol_checkpoint.cpp snapshots, checkpoints, restore and light-cone replay
-//   gol_profile.cpp    kernel timing, the in-kernel clock probe, gol_profile_*
+//   gol_profile.h      the accounting of pass timing as pure functions (no HIP, no
+//                      context) -- checked on the CPU (tests/profile_probe.cpp)
+//   gol_profile.cpp    the Profiler: per-pass event records and their fold, the
+//                      in-kernel clock probe's buffer, gol_profile_*
 //   gol_region.cpp     census, windowed pattern I/O and the density map
 //                      (gol_census, gol_read_region, gol_write_region,
 //                      gol_density)
@@ -50,6 +53,7 @@
 #include "../../include/gol.h"
 #include "gol_active.h"
 #include "gol_kernels.h"
+#include "gol_profile.h"
 
 struct LoopRing;  // gol_loopback.cpp
 
@@ -63,19 +67,6 @@ struct gol_group {
 
 #pragma GCC visibility push(hidden)
 namespace golc {
-
-// What a profiled event pair brackets (gol_profile_stats).
-enum ProfKind { kProfNone = -1, kProfMain = 0, kProfExchange = 1, kProfBoundary = 2 };
-
-struct EventPair {
-    hipEvent_t start = nullptr, stop = nullptr;
-    int clk_slot = -1;  // this launch's clock-probe slot (gol_stencil.h clock_probe_*), or -1
-    int kind = kProfMain;
-    int ref = -1;       // exchange / boundary pairs: index of the same pass's interior pair (this fold window)
-};
-
-// Clock-probe slots per context (one per profiled launch between folds).
-constexpr uint32_t kClockSlots = 1024;  // 4 KiB each
 
 // Generations a step plans, accumulates and folds at a time (step_chunks): the
 // hash accumulators are allocated for one chunk, 4 MiB.
@@ -128,6 +119,48 @@ struct Accum {
 struct LiveRows {
     bool known = true;  // false: any row may be non-zero (`runs` is empty then)
     golactive::Runs runs;
+};
+
+// The parts of a profiled pass (gol_profile_stats): its main launch (the whole
+// shard, or a sharded shard's interior rows), its halo exchange, its boundary launch.
+enum ProfKind { kProfNone = -1, kProfMain = 0, kProfExchange = 1, kProfBoundary = 2 };
+
+// One pass in the profiler's window.  Each part is a HIP event pair, created
+// the first time this record's part is used, and whether each event has been
+// recorded since the record was begun: the fold counts a part only if both were.
+struct PassRecord {
+    struct Part {
+        hipEvent_t start = nullptr, stop = nullptr;
+        bool started = false, stopped = false;
+    } part[3];          // by ProfKind
+    int clk_slot = -1;  // the main launch's clock-probe slot, or -1
+    uint32_t gens = 0;  // generations the main launch advances
+};
+
+// Pass timing of a context (gol_profile.cpp): the switch, the totals, the
+// window of pass records not yet folded into them and the clock-probe buffer.
+// A method's failure is its HIP status.
+struct Profiler {
+    static constexpr size_t kMaxPairs = 4096;      // event pairs of a window
+    static constexpr uint32_t kClockSlots = 1024;  // probe slots of a window, golprof::kClockSlotWords each
+    bool on = false;
+    golprof::Totals totals;  // since the last reset; the halo bytes are counted with the switch off too
+    std::vector<PassRecord> window;
+    size_t used = 0, pairs = 0;     // records begun and parts started since the last fold
+    Accum<unsigned long long> clk;  // in slots, zero when clean, device only; handed out in order,
+    uint32_t clk_used = 0;          // ... this many since the last fold
+
+    hipError_t alloc_clock(hipStream_t stream);  // the buffer exists and is zero; on failure nothing is held
+    // A record for the pass about to be enqueued (null: switched off).  Folds first when fewer than three
+    // pairs are left: the only fold besides the readers', so no pass straddles one.
+    hipError_t begin(PassRecord** rec, hipStream_t stream);
+    // Bracket part `kind` on the stream it runs on; stop() does nothing unless start() recorded.
+    hipError_t start(PassRecord* rec, ProfKind kind, hipStream_t stream);
+    hipError_t stop(PassRecord* rec, ProfKind kind, hipStream_t stream);
+    // The main launch advances `gens` generations; its probe slot, or null (no buffer, or none left).
+    unsigned long long* main_launch(PassRecord* rec, int gens);
+    hipError_t fold(hipStream_t stream);  // completed parts into the totals, used slots cleared; synchronises
+    void destroy_events();                // teardown: failures are logged
 };
 
 }  // namespace golc
@@ -195,20 +228,7 @@ struct gol_ctx {
     // tuning
     int32_t band_rows = 0;                                   // 0: automatic
     int32_t gens_per_pass = 0;                               // temporal blocking depth (0: automatic)
-    // profiling
-    bool prof = false;
-    std::vector<golc::EventPair> evs;
-    size_t evs_used = 0;
-    double prof_ms = 0.0;
-    uint64_t prof_launches = 0;
-    uint64_t prof_gens = 0;  // generations covered by the profiled launches
-    unsigned long long* clk_buf = nullptr;  // kClockSlots x kClockSlotWords u64 (device)
-    uint32_t clk_used = 0;                  // slots handed out since the last fold
-    double prof_clk_ms_ghz = 0.0, prof_clk_ms = 0.0;  // time-weighted probe clock
-    double prof_xchg_ms = 0.0, prof_bnd_ms = 0.0;     // halo exchanges (comm stream), boundary launches (edge)
-    double prof_xchg_exposed_ms = 0.0, prof_tail_ms = 0.0;  // ... how far they end after the interior launch
-    uint64_t prof_xchg = 0, prof_bnd = 0;
-    uint64_t halo_sent = 0, halo_recv = 0;             // bytes posted to the ring since the last reset
+    golc::Profiler profile;  // pass timing and the halo byte counters (gol_profile.cpp)
     // occupancy
     int num_cus = 0;
     mutable std::map<int, int64_t> occupancy_cache;  // resident_waves (a cache: const callers may fill it)
@@ -319,7 +339,8 @@ struct PassLaunch {
     PassSums sums;
     int n = 1;
     int32_t lo[2] = {0, 0}, hi[2] = {0, 0};
-    int prof_kind = kProfMain;
+    ProfKind prof_kind = kProfMain;  // the part of a profiled pass this launch is (kProfNone: untimed) ...
+    PassRecord* rec = nullptr;       // ... of this record; null: of a record of its own
     hipStream_t stream = nullptr;    // null: the compute stream
     const PlaneGeom* geom = nullptr;  // null: the context's own plane
 };
@@ -329,9 +350,10 @@ struct PassLaunch {
 // small-board test).
 int strip_count(const gol_ctx* ctx, gol::StepInstance k, bool halo_lanes = false);
 int launch_ranges(gol_ctx* ctx, const PassLaunch& launch);
-int sharded_interior(gol_ctx* ctx, int G, PassSums sums, bool has_up, bool has_down);
+// `rec`: the pass's profiling record (null: each launch opens its own).
+int sharded_interior(gol_ctx* ctx, int G, PassSums sums, bool has_up, bool has_down, PassRecord* rec);
 int sharded_boundary(gol_ctx* ctx, int G, PassSums sums, bool has_up, bool has_down, const hipEvent_t* halo_ready,
-                     int nready);
+                     int nready, PassRecord* rec);
 int sharded_pass_kernels(gol_ctx* ctx, int G, PassSums sums, bool has_up, bool has_down,
                          const hipEvent_t* halo_ready, int nready);
 int depth_cap(const gol_ctx* ctx);
@@ -402,11 +424,6 @@ size_t group_size(const gol_group* g);
 int group_step(gol_group* g, uint32_t generations, uint64_t* hashes_out, uint64_t* partials_out,
                uint64_t* populations_out);
 int64_t group_min_rows(const gol_group* g);
-
-// ---- profiling (gol_profile.cpp) -------------------------------------------
-
-EventPair* next_event_pair(gol_ctx* ctx);
-int fold_profile(gol_ctx* ctx);
 
 // ---- checkpoints (gol_checkpoint.cpp) --------------------------------------
 

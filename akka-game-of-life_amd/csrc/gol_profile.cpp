@@ -1,191 +1,184 @@
-// gol_profile.cpp -- kernel timing of a context (gol_profile_*): HIP event
-// pairs around the dominant launch of every pass (and, on a ring, around the
-// halo exchange and the boundary launch), folded into running totals, and the
-// in-kernel clock probe (gol_stencil.h clock_probe_*) each timed launch
-// writes into its own slot.
-#include <algorithm>
-#include <cstdarg>
-#include <cstdio>
-#include <cstring>
-#include <mutex>
-#include <string>
+// gol_profile.cpp -- pass timing of a context (gol_profile_*): the Profiler
+// keeps one record per profiled pass -- HIP event pairs around its main launch
+// and, on a ring, its halo exchange and boundary launch, plus the main
+// launch's clock-probe slot (gol_stencil.h clock_probe_*) -- and folds them
+// into running totals by the rules of gol_profile.h.
+#include <cstdlib>
 #include <vector>
 
 #include "gol_ctx.h"
 
-namespace {
-
-// Clock one launch ran at, from its probe slot (gol_stencil.h
-// clock_probe_*): core-clock ticks over 100 MHz reference ticks, summed over
-// the launch's workgroups.
-double slot_clock_ghz(const unsigned long long* w) {
-    unsigned long long mt = 0, rt = 0;
-    for (int k = 0; k < gol::kClockSubSlots; ++k) {
-        mt += w[k * gol::kClockSubWords + 0];
-        rt += w[k * gol::kClockSubWords + 1];
-    }
-    return rt ? (double)mt / (double)rt * 0.1 : 0.0;
-}
-
-}  // namespace
+static_assert(golprof::kClockSubSlots == gol::kClockSubSlots && golprof::kClockSubWords == gol::kClockSubWords &&
+                  golprof::kClockSlotWords == gol::kClockSlotWords,
+              "the fold reads a probe slot as the kernels write it");
 
 namespace golc {
 
-int fold_profile(gol_ctx* ctx) {
-    std::vector<float> times(ctx->evs_used, 0.f);
-    for (size_t i = 0; i < ctx->evs_used; ++i) {
-        HIP_CHECK(ctx, hipEventSynchronize(ctx->evs[i].stop));
-        HIP_CHECK(ctx, hipEventElapsedTime(&times[i], ctx->evs[i].start, ctx->evs[i].stop));
-    }
-    // every probed launch has finished (its stop event fired): read the slots
-    std::vector<unsigned long long> clk;
-    if (ctx->clk_used > 0) {
-        clk.resize((size_t)ctx->clk_used * gol::kClockSlotWords);
-        HIP_CHECK(ctx, hipMemcpy(clk.data(), ctx->clk_buf, clk.size() * sizeof(unsigned long long),
-                                 hipMemcpyDeviceToHost));
-    }
-    for (size_t i = 0; i < ctx->evs_used; ++i) {
-        const float ms = times[i];
-        const int kind = ctx->evs[i].kind, ref = ctx->evs[i].ref;
-        // exposed part: how long after its pass's interior launch this ended
-        float after = 0.f;
-        if ((kind == kProfExchange || kind == kProfBoundary) && ref >= 0 && (size_t)ref < i) {
-            HIP_CHECK(ctx, hipEventElapsedTime(&after, ctx->evs[ref].stop, ctx->evs[i].stop));
-            after = std::max(after, 0.f);
-        }
-        if (kind == kProfExchange) {
-            ctx->prof_xchg_ms += ms;
-            ctx->prof_xchg += 1;
-            // the part of the exchange the interior did not hide: never more than the exchange itself.  On
-            // a short shard the interior launch can end before the exchange's first event fires on the
-            // comm stream; the time between the two belongs to neither.
-            ctx->prof_xchg_exposed_ms += std::min(after, ms);
-            continue;
-        }
-        if (kind == kProfBoundary) {
-            ctx->prof_bnd_ms += ms;
-            ctx->prof_bnd += 1;
-            ctx->prof_tail_ms += after;
-            continue;
-        }
-        ctx->prof_ms += ms;
-        ctx->prof_launches += 1;
-        const int slot = ctx->evs[i].clk_slot;
-        if (slot >= 0 && (size_t)slot < (size_t)ctx->clk_used) {
-            const double ghz = slot_clock_ghz(clk.data() + (size_t)slot * gol::kClockSlotWords);
-            if (ghz > 0.0) {
-                ctx->prof_clk_ms_ghz += ghz * ms;
-                ctx->prof_clk_ms += ms;
-            }
-        }
-        ctx->evs[i].clk_slot = -1;
-    }
-    ctx->evs_used = 0;
-    if (ctx->clk_used > 0) {
-        HIP_CHECK(ctx, hipMemsetAsync(ctx->clk_buf, 0,
-                                      (size_t)ctx->clk_used * gol::kClockSlotWords * sizeof(unsigned long long),
-                                      ctx->compute));
-        HIP_CHECK(ctx, hipStreamSynchronize(ctx->compute));
-        ctx->clk_used = 0;
-    }
-    return GOL_OK;
+// Zeroes the first `slots` slots; a buffer that cannot be cleared is given up, not summed into again.
+static hipError_t clear_clock(Accum<unsigned long long>& clk, size_t slots, hipStream_t stream) {
+    hipError_t e = hipMemsetAsync(clk.dev, 0, slots * golprof::kClockSlotWords * sizeof(unsigned long long), stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(stream);
+    if (e == hipSuccess) clk.clean = clk.count;
+    else (void)clk.release();
+    return e;
 }
 
-EventPair* next_event_pair(gol_ctx* ctx) {
-    constexpr size_t kMaxPairs = 4096;
-    if (ctx->evs_used == ctx->evs.size()) {
-        if (ctx->evs.size() >= kMaxPairs) {
-            if (fold_profile(ctx) != GOL_OK) return nullptr;
-        } else {
-            EventPair e;
-            if (hipEventCreate(&e.start) != hipSuccess || hipEventCreate(&e.stop) != hipSuccess) {
-                (void)hipGetLastError();  // reported by the caller as GOL_EHIP
-                if (e.start) hip_note(hipEventDestroy(e.start), "hipEventDestroy");
-                return nullptr;
-            }
-            ctx->evs.push_back(e);
+hipError_t Profiler::alloc_clock(hipStream_t stream) {
+    const hipError_t e = clk.grow(kClockSlots, (size_t)kClockSlots * golprof::kClockSlotWords, 0);
+    return e == hipSuccess && clk.clean < clk.count ? clear_clock(clk, clk.count, stream) : e;
+}
+
+hipError_t Profiler::begin(PassRecord** rec, hipStream_t stream) {
+    *rec = nullptr;
+    if (!on) return hipSuccess;
+    if (kMaxPairs - pairs < 3 || used == kMaxPairs)  // (a record whose pass failed may hold no pair)
+        if (hipError_t e = fold(stream)) return e;
+    if (used == window.size()) window.emplace_back();
+    PassRecord& r = window[used++];
+    for (PassRecord::Part& p : r.part) p.started = p.stopped = false;
+    r.clk_slot = -1;
+    r.gens = 0;
+    *rec = &r;
+    return hipSuccess;
+}
+
+hipError_t Profiler::start(PassRecord* rec, ProfKind kind, hipStream_t stream) {
+    PassRecord::Part& p = rec->part[kind];
+    for (hipEvent_t* ev : {&p.start, &p.stop})
+        if (!*ev)
+            if (hipError_t e = hipEventCreate(ev)) return e;
+    if (hipError_t e = hipEventRecord(p.start, stream)) return e;
+    p.started = true;
+    ++pairs;
+    return hipSuccess;
+}
+
+hipError_t Profiler::stop(PassRecord* rec, ProfKind kind, hipStream_t stream) {
+    PassRecord::Part& p = rec->part[kind];
+    if (!p.started) return hipSuccess;
+    if (hipError_t e = hipEventRecord(p.stop, stream)) return e;
+    p.stopped = true;
+    return hipSuccess;
+}
+
+unsigned long long* Profiler::main_launch(PassRecord* rec, int gens) {
+    rec->gens = (uint32_t)gens;
+    if (!clk.count || clk_used >= kClockSlots) return nullptr;
+    clk.clean = 0;
+    rec->clk_slot = (int)clk_used++;
+    return clk.dev + (size_t)rec->clk_slot * golprof::kClockSlotWords;
+}
+
+hipError_t Profiler::fold(hipStream_t stream) {
+    // the HIP half: every part with both events recorded, into its pass's sample.  The exchange and the
+    // boundary launch are tied to the record's main launch (one that ran after them, a ring shard
+    // without interior rows, ended after them: they add 0)
+    std::vector<golprof::Sample> samples(used);
+    for (size_t i = 0; i < used; ++i) {
+        const PassRecord& r = window[i];
+        const PassRecord::Part& m = r.part[kProfMain];
+        golprof::Part* const out[3] = {&samples[i].main, &samples[i].exchange, &samples[i].boundary};
+        for (int k = 0; k < 3; ++k) {
+            const PassRecord::Part& p = r.part[k];
+            if (!(p.started && p.stopped)) continue;
+            const bool tied = k != kProfMain && m.started && m.stopped;
+            float ms = 0.f, after = 0.f;
+            if (hipError_t e = hipEventSynchronize(p.stop)) return e;
+            if (hipError_t e = hipEventElapsedTime(&ms, p.start, p.stop)) return e;
+            if (tied)
+                if (hipError_t e = hipEventElapsedTime(&after, m.stop, p.stop)) return e;
+            *out[k] = golprof::Part{true, tied, ms, after};
         }
+        samples[i].generations = r.gens;
     }
-    EventPair* ev = &ctx->evs[ctx->evs_used++];
-    ev->kind = kProfMain;
-    ev->clk_slot = -1;
-    ev->ref = -1;
-    return ev;
+    // every probed launch that counts has finished (its stop event fired): read the slots
+    if (clk_used > 0) {
+        std::vector<unsigned long long> words((size_t)clk_used * golprof::kClockSlotWords);
+        if (hipError_t e = hipMemcpy(words.data(), clk.dev, words.size() * sizeof(words[0]), hipMemcpyDeviceToHost))
+            return e;
+        for (size_t i = 0; i < used; ++i)
+            if (window[i].clk_slot >= 0)
+                samples[i].main_ghz =
+                    golprof::slot_clock_ghz(words.data() + (size_t)window[i].clk_slot * golprof::kClockSlotWords);
+    }
+    for (const golprof::Sample& s : samples) golprof::add(totals, s);  // the pure half
+    used = pairs = 0;
+    const size_t slots = clk_used;
+    clk_used = 0;
+    return slots ? clear_clock(clk, slots, stream) : hipSuccess;
+}
+
+void Profiler::destroy_events() {
+    for (PassRecord& r : window)
+        for (PassRecord::Part& p : r.part)
+            for (hipEvent_t ev : {p.start, p.stop})
+                if (ev) hip_note(hipEventDestroy(ev), "destroy: hipEventDestroy");
+    window.clear();
+    used = pairs = 0;
 }
 
 }  // namespace golc
 
 using namespace golc;
 
+namespace {
+
+// What every reader does first: the context's device, then the window into the totals.
+int folded(gol_ctx* ctx) {
+    if (int rc = bind(ctx)) return rc;
+    HIP_CHECK(ctx, ctx->profile.fold(ctx->compute));
+    return GOL_OK;
+}
+
+}  // namespace
+
 extern "C" {
 
 int gol_profile_enable(gol_ctx* ctx, int enable) {
     if (!ctx) return set_err(nullptr, GOL_EINVAL, "null context");
     const char* probe = getenv("GOL_CLOCK_PROBE");  // "0": no in-kernel clock probe (A/B)
-    if (enable && !ctx->clk_buf && !(probe && probe[0] == '0')) {
+    if (enable && !ctx->profile.clk.count && !(probe && probe[0] == '0')) {
         if (int rc = bind(ctx)) return rc;
-        const size_t bytes = (size_t)kClockSlots * gol::kClockSlotWords * sizeof(unsigned long long);
-        if (hipMalloc(&ctx->clk_buf, bytes) != hipSuccess) {
+        const hipError_t e = ctx->profile.alloc_clock(ctx->compute);
+        if (e == hipErrorOutOfMemory) {
             (void)hipGetLastError();
-            ctx->clk_buf = nullptr;
             return set_err(ctx, GOL_ENOMEM, "clock-probe buffer allocation failed");
         }
-        HIP_CHECK(ctx, hipMemset(ctx->clk_buf, 0, bytes));
+        HIP_CHECK(ctx, e);
     }
-    ctx->prof = enable != 0;
+    ctx->profile.on = enable != 0;
     return GOL_OK;
 }
 
 int gol_profile_clock(gol_ctx* ctx, double* ghz) {
     if (!ctx || !ghz) return set_err(ctx, GOL_EINVAL, "null argument");
-    if (int rc = bind(ctx)) return rc;
-    if (int rc = fold_profile(ctx)) return rc;
-    *ghz = ctx->prof_clk_ms > 0.0 ? ctx->prof_clk_ms_ghz / ctx->prof_clk_ms : 0.0;
+    if (int rc = folded(ctx)) return rc;
+    *ghz = golprof::clock_ghz(ctx->profile.totals);
     return GOL_OK;
 }
 
 int gol_profile_read(gol_ctx* ctx, double* total_ms, uint64_t* launches, uint64_t* generations) {
     if (!ctx) return set_err(nullptr, GOL_EINVAL, "null context");
-    if (int rc = bind(ctx)) return rc;
-    if (int rc = fold_profile(ctx)) return rc;
-    if (total_ms) *total_ms = ctx->prof_ms;
-    if (launches) *launches = ctx->prof_launches;
-    if (generations) *generations = ctx->prof_gens;
+    if (int rc = folded(ctx)) return rc;
+    const gol_profile_stats& st = ctx->profile.totals.stats;
+    if (total_ms) *total_ms = st.kernel_ms;
+    if (launches) *launches = st.launches;
+    if (generations) *generations = st.generations;
     return GOL_OK;
 }
 
 int gol_profile_reset(gol_ctx* ctx) {
     if (!ctx) return set_err(nullptr, GOL_EINVAL, "null context");
-    if (int rc = bind(ctx)) return rc;
-    if (int rc = fold_profile(ctx)) return rc;
-    ctx->prof_ms = 0.0;
-    ctx->prof_launches = 0;
-    ctx->prof_gens = 0;
-    ctx->prof_clk_ms_ghz = ctx->prof_clk_ms = 0.0;
-    ctx->prof_xchg_ms = ctx->prof_bnd_ms = 0.0;
-    ctx->prof_xchg_exposed_ms = ctx->prof_tail_ms = 0.0;
-    ctx->prof_xchg = ctx->prof_bnd = 0;
-    ctx->halo_sent = ctx->halo_recv = 0;
+    if (int rc = folded(ctx)) return rc;
+    ctx->profile.totals = golprof::Totals{};
     return GOL_OK;
 }
 
 int gol_profile_stats_read(gol_ctx* ctx, gol_profile_stats* out) {
     if (!ctx || !out) return set_err(ctx, GOL_EINVAL, "null argument");
-    if (int rc = bind(ctx)) return rc;
-    if (int rc = fold_profile(ctx)) return rc;
-    *out = gol_profile_stats{};
-    out->kernel_ms = ctx->prof_ms;
-    out->launches = ctx->prof_launches;
-    out->generations = ctx->prof_gens;
-    out->exchange_ms = ctx->prof_xchg_ms;
-    out->exchanges = ctx->prof_xchg;
-    out->boundary_ms = ctx->prof_bnd_ms;
-    out->boundary_launches = ctx->prof_bnd;
-    out->halo_bytes_sent = ctx->halo_sent;
-    out->halo_bytes_received = ctx->halo_recv;
-    out->clock_ghz = ctx->prof_clk_ms > 0.0 ? ctx->prof_clk_ms_ghz / ctx->prof_clk_ms : 0.0;
-    out->exchange_exposed_ms = ctx->prof_xchg_exposed_ms;
-    out->pass_tail_ms = ctx->prof_tail_ms;
+    if (int rc = folded(ctx)) return rc;
+    *out = ctx->profile.totals.stats;
+    out->clock_ghz = golprof::clock_ghz(ctx->profile.totals);
     return GOL_OK;
 }
 

@@ -58,6 +58,9 @@ int one_pass(gol_ctx* ctx, int G, PassSums sums) {
         const int down = (ctx->rank + 1) % ctx->nranks;
         const bool has_up = torus || ctx->rank > 0;
         const bool has_down = torus || ctx->rank < ctx->nranks - 1;
+        // profiling (null: off): the interior launch, the exchange and the boundary launch bracket their parts
+        PassRecord* rec = nullptr;
+        HIP_CHECK(ctx, ctx->profile.begin(&rec, ctx->compute));
         // G-deep halo exchange on the comm stream once the current plane is
         // final (ev_ready: recorded before this pass's interior launch, so the
         // exchange does not wait for it).  The interior launch is enqueued
@@ -67,10 +70,7 @@ int one_pass(gol_ctx* ctx, int G, PassSums sums) {
         // complete instead of blocking in ncclGroupEnd until someone aborts
         // the communicator.
         HIP_CHECK(ctx, hipEventRecord(ctx->ev_ready, ctx->compute));
-        const size_t evs_before = ctx->evs_used;
-        const int rc_interior = sharded_interior(ctx, G, sums, has_up, has_down);
-        // the interior launch's event pair (profiling; -1 if it has none in this fold window)
-        int iref = (ctx->prof && ctx->evs_used == evs_before + 1) ? (int)evs_before : -1;
+        const int rc_interior = sharded_interior(ctx, G, sums, has_up, has_down, rec);
         HIP_CHECK(ctx, hipStreamWaitEvent(ctx->comm, ctx->ev_ready, 0));
         const size_t cnt = (size_t)G * pitch;  // G contiguous rows (pitch padding included)
         // Issue order matters when up == down (2 ranks, or 1 rank sending to
@@ -84,36 +84,19 @@ int one_pass(gol_ctx* ctx, int G, PassSums sums) {
         if (has_up) ops[nops++] = {true, cur, cnt, up};
         if (has_up) ops[nops++] = {false, ctx->halo_top, cnt, up};
         if (has_down) ops[nops++] = {false, ctx->halo_bot, cnt, down};
-        // exchange timing (gol_profile_stats): comm-stream events around the group
-        EventPair* xev = nullptr;
-        if (ctx->prof && rc_interior == GOL_OK) {
-            xev = next_event_pair(ctx);
-            if (!xev) return set_err(ctx, GOL_EHIP, "profiling event allocation failed");
-            xev->kind = kProfExchange;
-            if ((int)ctx->evs_used - 1 <= iref) iref = -1;  // the allocation folded the window
-            xev->ref = iref;
-            HIP_CHECK(ctx, hipEventRecord(xev->start, ctx->comm));
-        }
-        for (int k = 0; k < nops; ++k) (ops[k].send ? ctx->halo_sent : ctx->halo_recv) += ops[k].count * 4;
+        // exchange timing (gol_profile_stats): comm-stream events around the group; a part left without its
+        // stop (a failed exchange) is skipped by the fold
+        if (rec && rc_interior == GOL_OK) HIP_CHECK(ctx, ctx->profile.start(rec, kProfExchange, ctx->comm));
+        gol_profile_stats& t = ctx->profile.totals.stats;
+        for (int k = 0; k < nops; ++k) (ops[k].send ? t.halo_bytes_sent : t.halo_bytes_received) += ops[k].count * 4;
         const int rc_x = ctx->loop ? loop_exchange(ctx, ops, nops) : rccl_exchange(ctx, ops, nops);
-        if (xev) {
-            if (rc_x == GOL_OK) {
-                HIP_CHECK(ctx, hipEventRecord(xev->stop, ctx->comm));
-            } else {
-                --ctx->evs_used;  // the pair stays unrecorded: hand it back (it was the last one taken)
-            }
-        }
+        if (rec && rc_x == GOL_OK) HIP_CHECK(ctx, ctx->profile.stop(rec, kProfExchange, ctx->comm));
         if (rc_interior) return rc_interior;
         if (rc_x) return rc_x;
         // The event covers the sends too: the next pass overwrites this plane
         // only after the boundary kernels, which wait for it.
         HIP_CHECK(ctx, hipEventRecord(ctx->ev_halo, ctx->comm));
-        const size_t evs_mid = ctx->evs_used;
-        int rc = sharded_boundary(ctx, G, sums, has_up, has_down, &ctx->ev_halo, 1);
-        if (rc) return rc;
-        if (ctx->prof && ctx->evs_used == evs_mid + 1 && ctx->evs[evs_mid].kind == kProfBoundary && iref >= 0 &&
-            (int)evs_mid > iref)
-            ctx->evs[evs_mid].ref = iref;
+        if (int rc = sharded_boundary(ctx, G, sums, has_up, has_down, &ctx->ev_halo, 1, rec)) return rc;
     }
     ctx->cur ^= 1;
     ctx->epoch += (uint64_t)G;

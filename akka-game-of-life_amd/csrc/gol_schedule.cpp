@@ -148,9 +148,9 @@ int strip_count(const gol_ctx* ctx, gol::StepInstance k, bool halo_lanes) {
     return (int)((ctx->wwords + sw - 1) / sw);
 }
 
-// Launch one pass (PassLaunch, gol_ctx.h).  Only the main launch of a pass
-// (whole shard, or the interior rows of a sharded shard) is bracketed by
-// profiling events: it is the dominant kernel.
+// Launch one pass (PassLaunch, gol_ctx.h).  With profiling on, the launch is
+// bracketed as the part L.prof_kind of the pass's record L.rec, or of a record
+// of its own (a pass of one timed launch: stepped whole, or a group shard's).
 int launch_ranges(gol_ctx* ctx, const PassLaunch& L) {
     const hipStream_t stream = L.stream ? L.stream : ctx->compute;
     const bool acc = L.sums.slots != nullptr;
@@ -186,31 +186,20 @@ int launch_ranges(gol_ctx* ctx, const PassLaunch& L) {
     p.birth = ctx->birth;
     p.survive = ctx->survive;
     p.xcd_chunk = golplan::xcd_chunk(L.gens, strips, xcd_chunk_env(), gol::kWavesPerWG);
-    EventPair* ev = nullptr;
-    p.clk = nullptr;
-    if (ctx->prof && L.prof_kind != kProfNone) {
-        ev = next_event_pair(ctx);
-        if (!ev) return set_err(ctx, GOL_EHIP, "profiling event allocation failed");
-        ev->kind = L.prof_kind;
-        if (L.prof_kind == kProfMain && ctx->clk_buf && ctx->clk_used < kClockSlots) {
-            ev->clk_slot = (int)ctx->clk_used++;
-            p.clk = ctx->clk_buf + (size_t)ev->clk_slot * gol::kClockSlotWords;
-        }
-        HIP_CHECK(ctx, hipEventRecord(ev->start, stream));
-    }
+    PassRecord* rec = L.prof_kind != kProfNone ? L.rec : nullptr;
+    if (!rec && L.prof_kind != kProfNone) HIP_CHECK(ctx, ctx->profile.begin(&rec, ctx->compute));
+    p.clk = rec && L.prof_kind == kProfMain ? ctx->profile.main_launch(rec, L.gens) : nullptr;
+    if (rec) HIP_CHECK(ctx, ctx->profile.start(rec, L.prof_kind, stream));
     HIP_CHECK(ctx, gol::launch_step(p, k, bp.grid, 1, stream));
-    if (ev) {
-        HIP_CHECK(ctx, hipEventRecord(ev->stop, stream));
-        if (L.prof_kind == kProfMain) ctx->prof_gens += (uint64_t)L.gens;
-    }
+    if (rec) HIP_CHECK(ctx, ctx->profile.stop(rec, L.prof_kind, stream));
     return GOL_OK;
 }
 
 // What every launch of a sharded pass shares: the planes, the received halos
 // at the plane's pitch and the accumulators.  A missing neighbour (clipped board
 // ends) reads dead rows: zero_row holds kMaxGensPerPass of them at the halo
-// pitch.  The caller sets the ranges, the profiling kind and the stream.
-static PassLaunch sharded_launch(gol_ctx* ctx, int G, PassSums sums, bool has_up, bool has_down) {
+// pitch.  The caller sets the ranges, the profiling part and the stream.
+static PassLaunch sharded_launch(gol_ctx* ctx, int G, PassSums sums, bool has_up, bool has_down, PassRecord* rec) {
     PassLaunch L;
     L.gens = G;
     L.cur = ctx->plane[ctx->cur];
@@ -219,16 +208,17 @@ static PassLaunch sharded_launch(gol_ctx* ctx, int G, PassSums sums, bool has_up
     L.halo_bot = has_down ? ctx->halo_bot : ctx->zero_row;
     L.halo_stride = ctx->pitch;
     L.sums = sums;
+    L.rec = rec;
     return L;
 }
 
 // The interior rows [G, rows - G) of a sharded pass on the compute stream:
 // they read no halo, so they are enqueued before the exchange (one_pass) and
 // run while it is in flight.  Shards of <= 2G rows have no interior.
-int sharded_interior(gol_ctx* ctx, int G, PassSums sums, bool has_up, bool has_down) {
+int sharded_interior(gol_ctx* ctx, int G, PassSums sums, bool has_up, bool has_down, PassRecord* rec) {
     const int32_t rows = (int32_t)ctx->rows;
     if (rows <= 2 * G) return GOL_OK;
-    PassLaunch L = sharded_launch(ctx, G, sums, has_up, has_down);
+    PassLaunch L = sharded_launch(ctx, G, sums, has_up, has_down, rec);
     L.lo[0] = G;
     L.hi[0] = rows - G;
     return launch_ranges(ctx, L);
@@ -236,14 +226,14 @@ int sharded_interior(gol_ctx* ctx, int G, PassSums sums, bool has_up, bool has_d
 
 // The rest of a sharded pass once every event in `halo_ready` has fired: the
 // two boundary row blocks on the edge stream, or the whole shard when it has
-// no interior.  The boundary launch runs concurrently with the tail of the
-// interior one (its waves take the slots the interior's waves free) instead
-// of after it; the compute stream then waits for it, so the next pass, a
-// snapshot or a hash sees the whole plane.
+// no interior (the pass's main launch then).  The boundary launch runs
+// concurrently with the tail of the interior one (its waves take the slots the
+// interior's waves free) instead of after it; the compute stream then waits
+// for it, so the next pass, a snapshot or a hash sees the whole plane.
 int sharded_boundary(gol_ctx* ctx, int G, PassSums sums, bool has_up, bool has_down, const hipEvent_t* halo_ready,
-                     int nready) {
+                     int nready, PassRecord* rec) {
     const int32_t rows = (int32_t)ctx->rows;
-    PassLaunch L = sharded_launch(ctx, G, sums, has_up, has_down);
+    PassLaunch L = sharded_launch(ctx, G, sums, has_up, has_down, rec);
     if (rows > 2 * G) {
         // The exchange events follow this pass's ev_ready, recorded on the
         // compute stream after the previous pass's boundary rows: every
@@ -269,11 +259,11 @@ int sharded_boundary(gol_ctx* ctx, int G, PassSums sums, bool has_up, bool has_d
 
 // Kernels of one sharded pass whose halos are already on their way (the
 // in-process group): the interior rows, then the boundary rows after
-// `halo_ready`.
+// `halo_ready`, each timed as a record of its own (not tied to one another).
 int sharded_pass_kernels(gol_ctx* ctx, int G, PassSums sums, bool has_up, bool has_down,
                          const hipEvent_t* halo_ready, int nready) {
-    if (int rc = sharded_interior(ctx, G, sums, has_up, has_down)) return rc;
-    return sharded_boundary(ctx, G, sums, has_up, has_down, halo_ready, nready);
+    if (int rc = sharded_interior(ctx, G, sums, has_up, has_down, nullptr)) return rc;
+    return sharded_boundary(ctx, G, sums, has_up, has_down, halo_ready, nready, nullptr);
 }
 
 // Deepest pass the context may run.  Every shard of a ring must pick the

@@ -456,7 +456,8 @@ int gol_profile_clock(gol_ctx* ctx, double* ghz);
  *       0 if before, summed: the part of the exchange the interior did not
  *       hide (so at most the exchange itself, where the interior ended before
  *       the exchange began), and the pass's whole critical path beyond the
- *       interior. */
+ *       interior.  The two sums cover ring passes: a shard of an in-process
+ *       group adds 0 to both. */
 typedef struct gol_profile_stats {
     double kernel_ms;
     uint64_t launches;

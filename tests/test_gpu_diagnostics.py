@@ -128,6 +128,115 @@ def test_loopback_stats_per_rank(gpu):
             e.close()
 
 
+FIGURES = ("kernel_ms", "launches", "generations", "exchange_ms", "exchanges", "boundary_ms", "boundary_launches",
+           "halo_bytes_sent", "halo_bytes_received", "clock_ghz", "exchange_exposed_ms", "pass_tail_ms")
+
+
+def test_profile_fold_on_a_ring(gpu):
+    """Three event pairs per pass: 1500 passes cross a fold of the 4096-pair
+    window, and every pass still counts once in every figure."""
+    from gameoflife import _native as N
+    W, H, gens = 2048, 16, 1500
+    board = O.seed_packed(W, H, 21)
+    with _engine(W, H) as e:
+        e.load(board)
+        e.comm_init(N.unique_id(), 0, 1)
+        e.set_tuning(gens_per_pass=1)
+        e.profile(True)
+        e.step(gens)
+        e.sync()
+        st = e.profile_stats()
+        assert st["launches"] == st["exchanges"] == st["boundary_launches"] == gens and st["generations"] == gens
+        assert st["halo_bytes_sent"] == st["halo_bytes_received"] == gens * 2 * 256
+        assert 0 <= st["exchange_exposed_ms"] <= st["exchange_ms"] + 1e-3 and st["pass_tail_ms"] >= 0
+        assert (e.snapshot() == O.run_packed(board, W, gens)[0]).all()
+
+
+def test_profile_fold_unsharded(gpu):
+    """One pair per pass: 4200 passes cross a fold, and a reset zeroes every figure."""
+    with _engine(1024, 8) as e:
+        e.seed(9)
+        e.set_tuning(gens_per_pass=1)
+        e.profile(True)
+        e.step(4200)
+        st = e.profile_stats()
+        assert st["launches"] == st["generations"] == 4200
+        assert st["exchanges"] == st["boundary_launches"] == 0 and 0 <= st["clock_ghz"] < 2.6
+        e.profile_reset()
+        st = e.profile_stats()
+        assert [st[k] for k in FIGURES] == [0] * len(FIGURES) and e.profile_clock() == 0.0
+
+
+def test_profile_ring_shard_without_interior(gpu):
+    """rows <= 2 G: the whole-shard launch is the pass's main launch, there is
+    no boundary launch, and the exchange (over before that launch begins) is
+    not exposed."""
+    from gameoflife import _native as N
+    W, H, G = 2048, 8, 4
+    board = O.seed_packed(W, H, 22)
+    with _engine(W, H) as e:
+        e.load(board)
+        e.comm_init(N.unique_id(), 0, 1)
+        e.set_tuning(gens_per_pass=G)
+        e.profile(True)
+        e.step(2 * G)
+        e.sync()
+        st = e.profile_stats()
+        assert st["launches"] == 2 and st["generations"] == 2 * G
+        assert st["boundary_launches"] == 0 and st["exchanges"] == 2
+        assert st["exchange_exposed_ms"] == 0 and st["pass_tail_ms"] == 0
+        assert (e.snapshot() == O.run_packed(board, W, 2 * G)[0]).all()
+
+
+def test_profile_group_shards(gpu):
+    """A group shard times its interior and boundary launches, untied: the two
+    sums over passes cover ring passes, and a group posts nothing to a ring."""
+    from gameoflife.engine import ShardGroup
+    W, H, G = 2048, 24, 2
+    board = O.seed_packed(W, H, 23)
+    shards = [_engine(W, H, row0=r0, rows=12) for r0 in (0, 12)]
+    try:
+        for s in shards:
+            s.set_tuning(gens_per_pass=G)
+            s.load(board[s.row0:s.row0 + 12])
+        with ShardGroup(shards) as g:
+            for s in shards:
+                s.profile(True)
+            g.step(3 * G)
+            g.sync()
+            for s in shards:
+                st = s.profile_stats()
+                assert st["launches"] == 3 and st["generations"] == 3 * G and st["boundary_launches"] == 3
+                assert st["exchanges"] == 0 and st["halo_bytes_sent"] == 0
+                assert st["exchange_exposed_ms"] == 0 and st["pass_tail_ms"] == 0
+    finally:
+        for s in shards:
+            s.close()
+
+
+def test_profile_active_rows_times_the_largest_run(gpu):
+    """A sparse pass launches once per run of live rows and times the largest
+    run's launch alone; `generations` counts the pass's whole depth.  (On 256
+    rows the two gliders' blocks, grown by the pass depth, cover the plane and
+    the passes run dense: 1024 rows keep them sparse.)"""
+    W, H, G = 1024, 1024, 4
+    cells = np.zeros((H, W), dtype=np.uint8)
+    for y0 in (10, 150):
+        for x, y in ((1, 0), (2, 1), (0, 2), (1, 2), (2, 2)):
+            cells[y0 + y, 100 + x] = 1
+    board = O.pack(cells)
+    with _engine(W, H, active_rows=True) as e:
+        e.load(board)
+        e.set_tuning(gens_per_pass=G)
+        e.profile(True)
+        e.step(2 * G)
+        e.sync()
+        assert e.active_stats()["sparse_passes"] == 2 and len(e.active_rows()) >= 2  # two runs per pass
+        st = e.profile_stats()
+        assert st["launches"] == 2 and st["generations"] == 2 * G
+        assert (e.snapshot() == O.run_packed(board, W, 2 * G)[0]).all()
+
+
 def test_loopback_peer_that_never_posts_fails_fast(gpu, monkeypatch):
     from gameoflife import _native as N
     monkeypatch.setenv("GOL_LOOPBACK_TIMEOUT_MS", "1500")
