@@ -4,7 +4,8 @@
 // the pass depth, what to clear in the destination plane, runs from the scan's
 // block bitmap, when to scan, when to give up and step the whole plane).
 // Standard library only -- no HIP, no context -- so tests/active_probe.cpp
-// checks it with a plain host compiler (tests/test_active_model.py).
+// checks it with a plain host compiler (tests/test_active_model.py), and
+// tests/find_probe.cpp the pattern search's anchor rows (tests/test_find_model.py).
 // gol_ring.cpp's one_pass applies it.  Results never depend on these choices.
 // DESIGN.md section 5c.
 #pragma once
@@ -96,6 +97,41 @@ inline Runs subtract(const Runs& a, const Runs& b) {
             lo = std::max(lo, b[k].hi);
         }
         if (lo < r.hi) out.push_back({lo, r.hi});
+    }
+    return out;
+}
+
+// Pattern search (gol_find): the anchor rows at which a
+// pattern `ph` rows tall can have a row inside `runs` -- every run grown
+// upward by ph - 1 rows, clamped at row 0 on a clipped board, wrapped and
+// split at the seam on a torus.  Sorted, disjoint, touching runs merged; exact
+// to the row (not block-aligned, no cap: there are at most twice the input's).
+inline Runs anchor_rows(const Runs& runs, int ph, int32_t rows, bool wrap_y) {
+    Runs grown;
+    for (const Run& r : runs) {
+        const int64_t hi = std::min<int64_t>(r.hi, rows), lo = (int64_t)std::max<int32_t>(r.lo, 0) - (ph - 1);
+        if (std::max<int32_t>(r.lo, 0) >= hi) continue;
+        grown.push_back({(int32_t)std::max<int64_t>(lo, 0), (int32_t)hi});
+        if (wrap_y && lo < 0) grown.push_back({(int32_t)std::max<int64_t>(lo + rows, 0), rows});
+    }
+    std::sort(grown.begin(), grown.end(), [](const Run& a, const Run& b) { return a.lo < b.lo; });
+    Runs out;
+    for (const Run& r : grown) {
+        if (!out.empty() && r.lo <= out.back().hi)
+            out.back().hi = std::max(out.back().hi, r.hi);
+        else
+            out.push_back(r);
+    }
+    return out;
+}
+
+// The rows of `a` inside [lo, hi) (a sorted and disjoint): the part of the
+// anchor rows one run of owned window rows launches.
+inline Runs clip(const Runs& a, int64_t lo, int64_t hi) {
+    Runs out;
+    for (const Run& r : a) {
+        const int64_t l = std::max<int64_t>(r.lo, lo), h = std::min<int64_t>(r.hi, hi);
+        if (l < h) out.push_back({(int32_t)l, (int32_t)h});
     }
     return out;
 }

@@ -147,6 +147,9 @@ void destroy_impl(gol_ctx* c) {
     hip_note(c->region_stage.release(), "destroy: window staging buffer");
     hip_note(c->census.release(), "destroy: census accumulators");
     hip_note(c->density.release(), "destroy: density map");
+    hip_note(c->find_cells.release(), "destroy: search pattern");
+    hip_note(c->find_count.release(), "destroy: search counters");
+    hip_note(c->find_hits.release(), "destroy: search hit list");
     hip_note(c->active_bits.release(), "destroy: active-row bitmap");
     hip_note(c->profile.clk.release(), "destroy: clock-probe buffer");
     for (hipStream_t st : {c->compute, c->comm, c->edge, c->xfer})

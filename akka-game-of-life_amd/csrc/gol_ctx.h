@@ -27,9 +27,10 @@
 //                      context) -- checked on the CPU (tests/profile_probe.cpp)
 //   gol_profile.cpp    the Profiler: per-pass event records and their fold, the
 //                      in-kernel clock probe's buffer, gol_profile_*
-//   gol_region.cpp     census, windowed pattern I/O and the density map
-//                      (gol_census, gol_read_region, gol_write_region,
-//                      gol_density)
+//   gol_region.cpp     census, windowed pattern I/O, the density map and the
+//                      pattern search (gol_census, gol_read_region,
+//                      gol_write_region, gol_density, gol_find; the search
+//                      kernel is gol_find.hip)
 //
 // Reference correspondence (src/main/scala/gameoflife/ of the reference):
 //   gol_create   <- BoardCreator.createAllInitialActors (BoardCreator.scala:79-89)
@@ -207,6 +208,12 @@ struct gol_ctx {
     golc::Accum<uint32_t> region_stage;
     golc::Accum<unsigned long long> census;
     golc::Accum<uint32_t> density;
+    // pattern search (gol_find): the cared cells (device and page-locked host
+    // words, in cells), the match counters (kFindWords, zero when clean; host:
+    // kFindValues) and the hit list (in (x, y) pairs, device only)
+    golc::Accum<uint32_t> find_cells;
+    golc::Accum<unsigned long long> find_count;
+    golc::Accum<long long> find_hits;
     // active-row stepping (gol_active.h, gol_active.cpp):
     // live[p] is kept for plane p by every writer of a plane, mode on or off
     golc::LiveRows live[2];                // gol_create clears both planes: known, no runs

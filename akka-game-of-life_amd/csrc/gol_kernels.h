@@ -1,8 +1,7 @@
 // gol_kernels.h -- internal interface between the C-ABI host layer
 // (gol_capi.cpp and the units gol_ctx.h lists) and the gfx950 kernels
 // (gol_stencil.h, gol_step.hip -- built once per pass depth --, gol_misc.hip,
-// gol_region.hip).  Not
-// installed.
+// gol_region.hip, gol_find.hip).  Not installed.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -247,5 +246,57 @@ hipError_t launch_density_fine(const uint32_t* src, int64_t pitch, int32_t wword
 // out[0..n) = grid[0..n), which is left zero; `out` may be mapped host memory
 // (one launch in place of a copy and the next call's memset).
 hipError_t launch_density_export(uint32_t* grid, uint32_t* out, int64_t n, hipStream_t stream);
+
+// ---- pattern search (gol_find.hip) --------------------------------------------
+
+// Match counters: kFindSlots sharded 64-bit counters one 64-byte line apart,
+// then (on a line of its own) the cursor of the hit list; zero when clean.
+constexpr int kFindSlots = 64;
+constexpr int kFindSlotStride = 8;  // u64 per slot
+constexpr int kFindCursorWord = kFindSlots * kFindSlotStride;
+constexpr int kFindWords = kFindCursorWord + kFindSlotStride;
+constexpr int kFindValues = 2;  // the fold's result: the count, the cursor
+
+// A cared cell of the pattern as the kernel reads it: row i, column k, state.
+constexpr uint32_t find_cell(int i, int k, bool alive) {
+    return (uint32_t)i | ((uint32_t)k << 8) | ((alive ? 1u : 0u) << 16);
+}
+
+// One launch searches anchor rows [a_lo, a_hi) (local rows) at the window's
+// columns: window word m holds anchor columns x0 + 32 m .. + 31 (modulo the
+// width on a torus), the last one under last_mask.  Pattern rows past `rows`
+// wrap into the plane (wrap_y: the shard is a whole torus) or read dead;
+// columns past the row wrap (wrap_x) or read dead.
+struct FindParams {
+    const uint32_t* plane;      // local row 0 of the current plane
+    const uint32_t* cells;      // ncells cared cells (find_cell), the live ones first
+    unsigned long long* slots;  // kFindWords counters
+    long long* hits;            // max_hits (x, y) pairs, or null (count only)
+    int64_t pitch;
+    int64_t max_hits;
+    int64_t grow0;              // global row of local row 0
+    int64_t x0, width;
+    int32_t wwords, rows;
+    int32_t a_lo, a_hi;
+    int32_t sw;                 // words of a window row = ceil(w / 32)
+    uint32_t last_mask;
+    int32_t c_first, sh;        // x0 / 32, x0 % 32
+    int32_t nw;                 // row-major words a lane reads per pattern row: 1 .. 4
+    int32_t ncells;
+    int32_t prefilter;          // the first cell of the list is live and the rows take 16-byte loads that wrap
+                                // whole (find_prefilter_fits): empty neighbourhoods are refused a KiB at a time
+    int32_t wrap_x, wrap_y;
+};
+// The prefilter reads the plane in 16-byte units: they must wrap whole on a
+// torus (every board of 128 k columns; the planes' alignment and pitch always
+// fit).  Without it every item runs the matching loop, which leaves after the
+// first cell's loads where nothing is alive.
+inline bool find_prefilter_fits(bool wrap_x, int32_t wwords) { return !wrap_x || wwords % 4 == 0; }
+// Adds the matches to the counters and their positions (global coordinates)
+// to the hit list; positions past max_hits are dropped.
+hipError_t launch_find(const FindParams& p, int ilv, hipStream_t stream);
+// out[0] = the counters' sum, out[1] = the cursor; all left zero.  `out` may
+// be mapped host memory.
+hipError_t launch_find_fold(unsigned long long* slots, unsigned long long* out, hipStream_t stream);
 
 }  // namespace gol

@@ -2,13 +2,16 @@
 // gol_census (population and bounding box, one pass on the device),
 // gol_read_region and gol_write_region (a window of the torus or of the
 // clipped board, gathered from / scattered into the device layout) and
-// gol_density (the live cells per tile of a window: the zoomed-out view).  They
+// gol_density (the live cells per tile of a window: the zoomed-out view) and
+// gol_find (every occurrence of a pattern among a window of anchors).  They
 // stand for what the reference offered at 7 x 7: the per-cell initialState of
 // BoardCreator.scala:65-70, the CellStateMsg stream a LoggerActor prints
 // (CellActor.scala:89, LoggerActor.scala:30-46) and the counting a reader of
 // that log does by eye.
 #include <algorithm>
 #include <cstring>
+#include <utility>
+#include <vector>
 
 #include "gol_ctx.h"
 
@@ -79,6 +82,19 @@ int ensure_density(gol_ctx* ctx, size_t words) {
     (void)hipGetLastError();
     return set_err(ctx, GOL_ENOMEM, "allocating %zu bytes for the density map on the device and the host failed",
                    words * sizeof(uint32_t));
+}
+
+// gol_find's device buffers: `cells` cared cells (device and page-locked host
+// words), the counters, and a hit list of `pairs` (x, y) pairs.  Nothing is in
+// flight on them between calls: gol_find synchronises before it returns.
+int ensure_find(gol_ctx* ctx, size_t cells, size_t pairs) {
+    hipError_t e = ctx->find_cells.grow(cells, cells, cells);
+    if (e == hipSuccess) e = ctx->find_count.grow(1, gol::kFindWords, gol::kFindValues);
+    if (e == hipSuccess && pairs) e = ctx->find_hits.grow(pairs, 2 * pairs, 0);
+    if (e == hipSuccess) return GOL_OK;
+    (void)hipGetLastError();
+    return set_err(ctx, GOL_ENOMEM, "allocating the pattern (%zu cells) and a hit list of %zu matches on the device failed",
+                   cells, pairs);
 }
 
 }  // namespace
@@ -225,6 +241,118 @@ int gol_density(gol_ctx* ctx, int64_t x0, int64_t y0, int64_t w, int64_t h, int3
             const uint32_t* __restrict__ in = got;
             for (int64_t j = 0; j < tw; ++j) out[j] += in[j];
         }
+    return GOL_OK;
+}
+
+int gol_find(gol_ctx* ctx, int64_t x0, int64_t y0, int64_t w, int64_t h, const uint32_t* pattern, const uint32_t* care,
+             int64_t pattern_pitch_words, int32_t pw, int32_t ph, int64_t* xy_out, int64_t max_matches,
+             gol_find_result* out) {
+    if (!ctx) return set_err(nullptr, GOL_EINVAL, "gol_find: null context");
+    if (!pattern || !out) return set_err(ctx, GOL_EINVAL, "gol_find: null pattern or result");
+    if (max_matches < 0 || (max_matches > 0 && !xy_out))
+        return set_err(ctx, GOL_EINVAL, "gol_find: max_matches %lld %s", (long long)max_matches,
+                       max_matches < 0 ? "is negative" : "with a null xy_out");
+    if (pw < 1 || pw > 64 || ph < 1 || ph > 64 || pw > ctx->width || ph > ctx->height)
+        return set_err(ctx, GOL_EINVAL, "gol_find: a %d x %d pattern is not within 1 .. 64 each way and a %lld x %lld board",
+                       pw, ph, (long long)ctx->width, (long long)ctx->height);
+    if (pattern_pitch_words < (pw + 31) / 32)
+        return set_err(ctx, GOL_EINVAL, "gol_find: pattern pitch %lld < %d words per pattern row",
+                       (long long)pattern_pitch_words, (pw + 31) / 32);
+    if (int rc = check_window(ctx, "gol_find", x0, y0, w, h, pattern)) return rc;
+    // the cared cells, live ones first, each group row by row: the kernel loads a pattern row when the
+    // list reaches it
+    std::vector<uint32_t> cells[2];  // [dead, live]
+    for (int i = 0; i < ph; ++i)
+        for (int k = 0; k < pw; ++k) {
+            const int64_t word = i * pattern_pitch_words + k / 32;
+            if (care && !((care[word] >> (k % 32)) & 1u)) continue;
+            const bool alive = (pattern[word] >> (k % 32)) & 1u;
+            cells[alive].push_back(gol::find_cell(i, k, alive));
+        }
+    const size_t ncells = cells[0].size() + cells[1].size();
+    if (ncells == 0) return set_err(ctx, GOL_EINVAL, "gol_find: the care mask cares for no cell of the pattern");
+    const bool has_live = !cells[1].empty();
+
+    gol_find_result res{0, 0, 0};
+    // The anchor rows this shard examines: the window's rows it owns whose pattern rows are all its own
+    // (a whole torus wraps) or off the end of a clipped board.
+    const bool wrap_y = ctx->topology == GOL_TORUS && ctx->rows == ctx->height;
+    const bool open_end = wrap_y || (ctx->topology == GOL_REF_CLIPPED && ctx->row0 + ctx->rows == ctx->height);
+    const int64_t a_end = open_end ? ctx->rows : ctx->rows - (ph - 1);  // anchors: local rows [0, a_end)
+    RowRun runs[2];
+    const int nruns = owned_runs(ctx, y0, h, runs);
+    // ... of them, where the live rows are known and the pattern has a live cared cell, those with a
+    // pattern row in a run
+    const LiveRows& live = ctx->live[ctx->cur];
+    const bool narrowed = live.known && has_live;
+    const golactive::Runs can_match =
+        narrowed ? golactive::anchor_rows(live.runs, ph, (int32_t)ctx->rows, wrap_y) : golactive::Runs{};
+    golactive::Runs todo;
+    for (int k = 0; k < nruns; ++k) {
+        const int64_t lo = runs[k].local_row, hi = std::min(runs[k].local_row + runs[k].count, a_end);
+        if (lo >= hi) continue;
+        if (narrowed)
+            for (const golactive::Run& r : golactive::clip(can_match, lo, hi)) todo.push_back(r);
+        else
+            todo.push_back({(int32_t)lo, (int32_t)hi});
+    }
+    res.rows_searched = (uint64_t)golactive::row_count(todo);
+    if (todo.empty()) {  // the window misses the shard, or no row of it can hold a match
+        *out = res;
+        return GOL_OK;
+    }
+    if (int rc = bind(ctx)) return rc;
+    if (int rc = ensure_find(ctx, ncells, (size_t)max_matches)) return rc;
+    std::copy(cells[1].begin(), cells[1].end(), ctx->find_cells.host);
+    std::copy(cells[0].begin(), cells[0].end(), ctx->find_cells.host + cells[1].size());
+    // On the compute stream: after every queued pass and after the device copy of a snapshot in flight;
+    // the board, the epoch, the hash and the live-row lists stay.
+    Accum<unsigned long long>& acc = ctx->find_count;
+    HIP_CHECK(ctx, hipMemcpyAsync(ctx->find_cells.dev, ctx->find_cells.host, ncells * sizeof(uint32_t),
+                                  hipMemcpyHostToDevice, ctx->compute));
+    if (!acc.clean) HIP_CHECK(ctx, hipMemsetAsync(acc.dev, 0, gol::kFindWords * sizeof(unsigned long long), ctx->compute));
+    acc.clean = 0;  // in use until the fold has left the counters zero
+    gol::FindParams p{};
+    p.plane = ctx->plane[ctx->cur];
+    p.cells = ctx->find_cells.dev;
+    p.slots = acc.dev;
+    p.hits = max_matches ? ctx->find_hits.dev : nullptr;
+    p.pitch = ctx->pitch;
+    p.max_hits = max_matches;
+    p.grow0 = ctx->row0;
+    p.x0 = x0;
+    p.width = ctx->width;
+    p.wwords = ctx->wwords;
+    p.rows = (int32_t)ctx->rows;
+    p.sw = (int32_t)((w + 31) / 32);
+    p.last_mask = w % 32 ? (uint32_t)((1ull << (w % 32)) - 1ull) : 0xFFFFFFFFu;
+    p.c_first = (int32_t)(x0 / 32);
+    p.sh = (int32_t)(x0 % 32);
+    p.nw = ((p.sh + pw + 30) >> 5) + 1;  // anchor bit 31's column pw - 1 is bit sh + 31 + pw - 1 of the lane's words
+    p.ncells = (int32_t)ncells;
+    p.prefilter = has_live && gol::find_prefilter_fits(ctx->topology == GOL_TORUS, ctx->wwords);
+    p.wrap_x = ctx->topology == GOL_TORUS;
+    p.wrap_y = wrap_y;
+    for (const golactive::Run& r : todo) {
+        p.a_lo = r.lo;
+        p.a_hi = r.hi;
+        HIP_CHECK(ctx, gol::launch_find(p, ctx->ilv, ctx->compute));
+    }
+    HIP_CHECK(ctx, gol::launch_find_fold(acc.dev, acc.host_dev, ctx->compute));
+    HIP_CHECK(ctx, hipStreamSynchronize(ctx->compute));
+    acc.clean = 1;
+    res.count = acc.host[0];
+    res.returned = std::min<uint64_t>(res.count, (uint64_t)max_matches);
+    if (res.returned) {
+        HIP_CHECK(ctx, hipMemcpyAsync(xy_out, ctx->find_hits.dev, (size_t)res.returned * 2 * sizeof(int64_t),
+                                      hipMemcpyDeviceToHost, ctx->compute));
+        HIP_CHECK(ctx, hipStreamSynchronize(ctx->compute));
+        std::vector<std::pair<int64_t, int64_t>> yx((size_t)res.returned);  // the host sorts: by (y, x)
+        for (size_t k = 0; k < yx.size(); ++k) yx[k] = {xy_out[2 * k + 1], xy_out[2 * k]};
+        std::sort(yx.begin(), yx.end());
+        for (size_t k = 0; k < yx.size(); ++k) xy_out[2 * k] = yx[k].second, xy_out[2 * k + 1] = yx[k].first;
+    }
+    *out = res;
     return GOL_OK;
 }
 

@@ -96,6 +96,14 @@ class GolCensusResult(ctypes.Structure):
     ]
 
 
+class GolFindResult(ctypes.Structure):
+    _fields_ = [
+        ("count", ctypes.c_uint64),
+        ("returned", ctypes.c_uint64),
+        ("rows_searched", ctypes.c_uint64),
+    ]
+
+
 class GolActiveStats(ctypes.Structure):
     _fields_ = [
         ("passes", ctypes.c_uint64),
@@ -180,6 +188,8 @@ _SIGNATURES = {
     "gol_write_region": (_c.c_int, [_vp, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_int64, _u32p, _c.c_int64,
                                     _c.c_int32]),
     "gol_density": (_c.c_int, [_vp, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_int32, _u32p, _c.c_int64]),
+    "gol_find": (_c.c_int, [_vp, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_int64, _u32p, _u32p, _c.c_int64, _c.c_int32,
+                            _c.c_int32, ctypes.POINTER(_c.c_int64), _c.c_int64, ctypes.POINTER(GolFindResult)]),
     "gol_set_active_rows": (_c.c_int, [_vp, _c.c_int32]),
     "gol_active_stats_read": (_c.c_int, [_vp, ctypes.POINTER(GolActiveStats), _c.c_int32]),
     "gol_active_rows": (_c.c_int, [_vp, ctypes.POINTER(_c.c_int64), _c.c_int32, ctypes.POINTER(_c.c_int32)]),

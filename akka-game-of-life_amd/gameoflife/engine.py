@@ -220,6 +220,37 @@ class GolEngine:
         self._density_into(x, y, w, h, lg, counts)
         return counts
 
+    def _find_raw(self, cells: np.ndarray, care: np.ndarray, x: int, y: int, w: int, h: int,
+                  max_matches: int) -> tuple[int, np.ndarray, int]:
+        """gol_find with a prepared pattern (patterns.as_search): (count,
+        int64 [m][2] matches sorted by (y, x), rows searched) of this shard."""
+        pat, mask = codec.pack(cells), codec.pack(care)
+        xy = np.zeros((max(int(max_matches), 0), 2), dtype=np.int64)
+        res = N.GolFindResult()
+        self._chk(N.lib.gol_find(self._h, x, y, w, h, pat.ctypes.data_as(N._u32p), mask.ctypes.data_as(N._u32p),
+                                 pat.shape[1], cells.shape[1], cells.shape[0],
+                                 xy.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)) if xy.size else None,
+                                 max_matches, ctypes.byref(res)))
+        return int(res.count), xy[:res.returned], int(res.rows_searched)
+
+    def find(self, pattern, care=None, border: int = 0, x: int = 0, y: int = 0, w: int | None = None,
+             h: int | None = None, max_matches: int = 65536) -> dict:
+        """Every occurrence of a pattern, searched on the device (gol_find):
+        {"count": n, "matches": int64 [m][2] of (x, y), "rows_searched": r}.
+        `pattern`, `care` and `border` as patterns.as_search takes them
+        (border=1: the object standing alone).  (x, y, w, h) is a window of
+        anchors -- the board cells under the pattern's top-left cell -- with
+        density()'s defaults; the pattern may reach past it, wrapping on a
+        torus and reading dead beyond a clipped board.  `count` is exact;
+        `matches` holds min(count, max_matches) of them in global
+        coordinates, sorted by (y, x).  A shard of a larger board examines only
+        the anchors whose pattern lies in its own rows (ShardGroup.find
+        completes the rest)."""
+        cells, mask = patterns.as_search(pattern, care, border)
+        w, h = _density_window(self, x, y, w, h)
+        n, xy, rows = self._find_raw(cells, mask, x, y, w, h, max_matches)
+        return {"count": n, "matches": xy, "rows_searched": rows}
+
     def checkpoint(self) -> np.ndarray:
         """gol_checkpoint into a new uint8 array (a bytes-like buffer: file
         writes, parse_checkpoint and restore take it as is).  No zero-fill and
@@ -445,6 +476,57 @@ class ShardGroup:
         for s in self.shards:
             s._density_into(x, y, w, h, lg, counts)
         return counts
+
+    def _band(self, x: int, y: int, w: int, h: int) -> np.ndarray:
+        """Board cells (x + j, y + i), j < w, i < h, with y inside the board:
+        wrapped on a torus (however often), dead beyond a clipped board."""
+        e = self.shards[0]
+        if e.topology == "torus":
+            base = self.read_region(x % e.width, y, min(w, e.width), min(h, e.height))
+            return base[np.arange(h) % base.shape[0]][:, np.arange(w) % base.shape[1]]
+        band = np.zeros((h, w), dtype=np.uint8)
+        sw, sh = min(w, e.width - x), min(h, e.height - y)
+        if sw > 0 and sh > 0:
+            band[:sh, :sw] = self.read_region(x, y, sw, sh)
+        return band
+
+    def find(self, pattern, care=None, border: int = 0, x: int = 0, y: int = 0, w: int | None = None,
+             h: int | None = None, max_matches: int = 65536) -> dict:
+        """The board's matches (GolEngine.find): the same search on every
+        shard, the counts summed, the matches merged and sorted.  The anchors
+        no shard examines -- those of the window in the last ph - 1 rows above
+        a shard boundary (the torus seam between the last and the first shard
+        included), whose pattern straddles it -- are matched here on the host,
+        in the band of rows around the boundary read with read_region."""
+        cells, mask = patterns.as_search(pattern, care, border)
+        ph, pw = cells.shape
+        e0 = self.shards[0]
+        torus = e0.topology == "torus"
+        w, h = _density_window(e0, x, y, w, h)
+        count = rows = 0
+        found = []
+        for s in self.shards:
+            n, xy, r = s._find_raw(cells, mask, x, y, w, h, max_matches)
+            count, rows = count + n, rows + r
+            found.append(xy)
+        for s in self.shards:
+            end = s.row0 + s.rows
+            if ph == 1 or (s.rows == e0.height if torus else end == e0.height):
+                continue  # the shard examines every anchor row it owns
+            first = max(s.row0, end - (ph - 1))  # its anchor rows [first, end) were left out
+            ys = np.arange(first, end)
+            ys = ys[((ys - y) % e0.height < h) if torus else ((ys >= y) & (ys < y + h))]
+            if not ys.size:
+                continue
+            band = self._band(x, first, w + pw - 1, end - first + ph - 1)
+            hit = patterns.match_band(band, cells, mask)[ys - first]
+            j, i = np.nonzero(hit)
+            xs = (x + i) % e0.width if torus else x + i
+            count += int(j.size)
+            found.append(np.stack([xs, ys[j]], axis=1).astype(np.int64).reshape(-1, 2))
+        xy = np.concatenate(found) if found else np.zeros((0, 2), dtype=np.int64)
+        xy = xy[np.lexsort((xy[:, 0], xy[:, 1]))][:max(int(max_matches), 0)]
+        return {"count": count, "matches": xy, "rows_searched": rows}
 
     def hash(self) -> int:
         """The board's state hash: the shards' partials summed mod 2^64."""

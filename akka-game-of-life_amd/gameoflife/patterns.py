@@ -149,3 +149,64 @@ def as_cells(pattern) -> np.ndarray:
     if c.ndim != 2 or c.shape[0] < 1 or c.shape[1] < 1:
         raise ValueError("a pattern is a non-empty [h][w] cell array")
     return c
+
+
+SEARCH_MAX = 64  # gol_find: a pattern of at most 64 x 64 cells, border included
+
+
+def as_search(pattern, care=None, border: int = 0) -> tuple[np.ndarray, np.ndarray]:
+    """A pattern to search for (GolEngine.find) as (cells, care): two uint8
+    [h][w] arrays, care 1 where the board must equal the pattern and 0 where
+    anything goes.  `pattern` is any form as_cells takes; a list of rows may
+    also use `?` for a cell that is not cared for.  `care` (optional) is a cell
+    array of the pattern's shape.  border=n surrounds the pattern with n rings
+    of cared dead cells: the search for the object standing alone.  ValueError
+    for a result outside 64 x 64, a care array of another shape and a pattern
+    with no cared cell."""
+    asked = None
+    if isinstance(pattern, (list, tuple)) and pattern and all(isinstance(r, str) for r in pattern):
+        rows = list(pattern)
+        cells = from_rows([r.replace("?", ".") for r in rows])
+        asked = np.ones_like(cells)
+        for y, r in enumerate(rows):
+            for x, ch in enumerate(r):
+                if ch == "?":
+                    asked[y, x] = 0
+    else:
+        cells = as_cells(pattern)
+    if care is not None:
+        c = np.asarray(care)
+        if c.shape != cells.shape:
+            raise ValueError(f"the care mask's shape {c.shape} is not the pattern's {cells.shape}")
+        c = (c != 0).astype(np.uint8)
+        asked = c if asked is None else asked & c
+    if asked is None:
+        asked = np.ones_like(cells)
+    if not isinstance(border, (int, np.integer)) or isinstance(border, bool) or border < 0:
+        raise ValueError(f"border must be a ring count >= 0, not {border!r}")
+    if border:
+        cells = np.pad(cells, border, constant_values=0)
+        asked = np.pad(asked, border, constant_values=1)
+    if cells.shape[0] > SEARCH_MAX or cells.shape[1] > SEARCH_MAX:
+        raise ValueError(f"a search pattern is at most {SEARCH_MAX} x {SEARCH_MAX} cells, border included; "
+                         f"this one is {cells.shape[1]} x {cells.shape[0]}")
+    if not asked.any():
+        raise ValueError("the search pattern cares for no cell")
+    return np.ascontiguousarray(cells & asked, dtype=np.uint8), np.ascontiguousarray(asked, dtype=np.uint8)
+
+
+def match_band(band, cells, care) -> np.ndarray:
+    """Host matcher for the few anchors a device search leaves to its caller
+    (ShardGroup.find): bool [bh - ph + 1][bw - pw + 1], entry (j, i) true iff
+    the [bh][bw] cell array `band` equals the pattern at its rows j .. j + ph - 1
+    and columns i .. i + pw - 1 in every cared cell.  The caller has wrapped or
+    padded the band."""
+    band = np.asarray(band, dtype=np.uint8)
+    ph, pw = cells.shape
+    nh, nw = band.shape[0] - ph + 1, band.shape[1] - pw + 1
+    if nh < 1 or nw < 1:
+        return np.zeros((max(nh, 0), max(nw, 0)), dtype=bool)
+    ok = np.ones((nh, nw), dtype=bool)
+    for i, k in zip(*np.nonzero(care)):
+        ok &= band[i:i + nh, k:k + nw] == cells[i, k]
+    return ok

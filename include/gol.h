@@ -55,7 +55,8 @@ extern "C" {
  * gol_read_region, gol_write_region and gol_density were added without a new
  * version: additive entry points change nothing a version-2 caller relies on.
  * So were gol_set_active_rows, gol_active_stats_read and gol_active_rows, and
- * gol_step_series and gol_group_step_series (the fused population series). */
+ * gol_step_series and gol_group_step_series (the fused population series),
+ * and gol_find (the pattern search). */
 #define GOL_ABI_VERSION 2
 
 /* Return codes. */
@@ -348,6 +349,68 @@ int gol_write_region(gol_ctx* ctx, int64_t x0, int64_t y0, int64_t w, int64_t h,
  * grows on demand (GOL_ENOMEM if a map does not fit: 32 bits per tile). */
 int gol_density(gol_ctx* ctx, int64_t x0, int64_t y0, int64_t w, int64_t h, int32_t log2_tile,
                 uint32_t* counts, int64_t pitch);
+
+/* Pattern search: every occurrence of a pattern on the board, found on the
+ * device.  Replaces reading "what is where" off the LoggerActor's board dump
+ * (LoggerActor.scala:30-46) -- how many gliders a gun has emitted, whether an
+ * eater still stands at (x, y) -- which a host can only do after
+ * gol_read_region has shipped the area: one pass over the rows that can hold a
+ * match, and only the positions cross the bus.
+ *
+ * `pattern` and `care` are ph rows of packed words in the window layout above
+ * (pattern column k is bit k % 32 of word k / 32, rows pattern_pitch_words
+ * apart, pattern_pitch_words >= ceil(pw / 32)).  A care bit of 1: the cell must
+ * equal the pattern bit; 0: don't care.  care = NULL cares for every cell of
+ * the pw x ph box.  Bits at k >= pw are ignored in both.  1 <= pw <= 64,
+ * 1 <= ph <= 64, pw <= width, ph <= height, at least one cared cell; a pattern
+ * with no live cared cell (an empty 3 x 3 box) is legal.
+ *
+ * The window (x0, y0, w, h) follows the rules of gol_read_region above and is
+ * a window of ANCHORS: an anchor is the board cell under the pattern's
+ * top-left cell; the pattern itself may extend past the window.  Anchor (x, y)
+ * matches iff for every cared cell (k, i) board cell (x + k, y + i) equals
+ * pattern cell (k, i); the coordinates wrap modulo width and height on a
+ * torus; on GOL_REF_CLIPPED cells beyond the stored board read dead, and the
+ * stored cells outside the visible extent are cells like any other, as in
+ * gol_census.
+ *
+ * out->count is exact.  xy_out receives out->returned = min(count,
+ * max_matches) pairs (x, y) in global board coordinates, sorted by (y, x);
+ * when count > max_matches they are some max_matches distinct matches, which
+ * ones is unspecified.  max_matches = 0 with xy_out = NULL counts only.
+ *
+ * A shard examines the window's anchor rows it owns whose pattern rows
+ * y .. y + ph - 1 are each one of its own rows or off the end of a clipped
+ * board (a shard that owns the whole height of a torus therefore wraps).
+ * Anchors whose pattern straddles a shard boundary are examined by no shard:
+ * a sharded caller issues the same call on every shard, sums the counts,
+ * merges the lists and completes the anchors in the last ph - 1 rows above
+ * each boundary from a gol_read_region band (gameoflife.engine.ShardGroup.find
+ * does).  A window that misses the shard returns GOL_OK with a zeroed result.
+ * out->rows_searched is the number of anchor rows the search kernels were
+ * launched over: where the rows that can hold a live cell are known
+ * (gol_active_rows) and the pattern has a live cared cell, only anchor rows
+ * with a pattern row inside them; results never depend on it.
+ *
+ * A null context, pattern or result, max_matches < 0, max_matches > 0 with a
+ * null xy_out, sizes outside the limits, a short pitch, no cared cell and a
+ * window out of range return GOL_EINVAL with a message before any device work
+ * is queued, and leave xy_out and *out untouched.  The call is ordered on the
+ * compute stream after every queued pass and after the device copy of a
+ * snapshot in flight, and synchronises before it returns; it changes neither
+ * the board, the epoch, the hash nor the live-row lists, and is valid with a
+ * communicator, a loopback ring or a group attached.  The device buffers
+ * (pattern, counters, hit list) belong to the context and grow on demand
+ * (GOL_ENOMEM if they cannot: 16 bytes per match of max_matches). */
+typedef struct gol_find_result {
+    uint64_t count;          /* matches among the anchors this call examined            */
+    uint64_t returned;       /* pairs written to xy_out: min(count, max_matches)        */
+    uint64_t rows_searched;  /* anchor rows the search kernels were launched over       */
+} gol_find_result;
+int gol_find(gol_ctx* ctx, int64_t x0, int64_t y0, int64_t w, int64_t h,
+             const uint32_t* pattern, const uint32_t* care, int64_t pattern_pitch_words,
+             int32_t pw, int32_t ph,
+             int64_t* xy_out, int64_t max_matches, gol_find_result* out);
 
 /* Shard checkpoint = {header with epoch + geometry, packed board}.  Replaces
  * the reference's recovery state (initialState kept by the frontend,
