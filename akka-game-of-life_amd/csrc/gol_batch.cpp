@@ -1,0 +1,302 @@
+// gol_batch.cpp -- C ABI of the batch engine (include/gol.h gol_batch_*;
+// DESIGN.md section 5f): many independent boards of at most 64 x 64 stored
+// cells stepped by one launch (kernels: gol_batch.hip).  A handle type of its
+// own: it shares the error conventions and the HIP status discipline with the
+// contexts (gol_ctx.h), and nothing else -- no planner, no step kernel.
+#include <algorithm>
+#include <cstdarg>
+#include <cstdio>
+#include <string>
+#include <vector>
+
+#include "gol_batch.h"
+#include "gol_ctx.h"
+
+struct gol_batch {
+    golbatch::Geometry geo{};
+    golbatch::Lanes lanes{};
+    uint32_t birth = 0, survive = 0;
+    int device = 0;
+    uint32_t chunk = 0;  // gol_batch_set_chunk (0: automatic)
+    uint64_t epoch = 0;
+    hipStream_t stream = nullptr;
+    unsigned long long* plane = nullptr;  // boards * height rows
+    unsigned long long* prev = nullptr;   // the plane one generation before (settle detection across launches)
+    uint32_t* settled = nullptr;          // [boards]
+    // the series of one launch, [boards][series_gens] (grown on demand), and gol_batch_hashes' results
+    uint32_t* series = nullptr;
+    size_t series_gens = 0;
+    unsigned long long* hashes = nullptr;
+    uint32_t* hash_pops = nullptr;
+    size_t hashes_count = 0;
+    std::string err;
+};
+
+namespace {
+
+using golc::hip_note;
+
+int batch_err(gol_batch* b, int code, const char* fmt, ...) {
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    if (b) {
+        b->err = buf;
+        return code;
+    }
+    return golc::set_err(nullptr, code, "%s", buf);
+}
+
+// A failing HIP call's status is reported through the return code and taken
+// off the thread.
+int batch_hip_fail(gol_batch* b, hipError_t e, const char* expr, int line) {
+    (void)hipGetLastError();
+    return batch_err(b, GOL_EHIP, "%s failed: %s (gol_batch.cpp:%d)", expr, hipGetErrorString(e), line);
+}
+
+#define BATCH_HIP(b, expr)                                                        \
+    do {                                                                          \
+        const hipError_t e_ = (expr);                                             \
+        if (e_ != hipSuccess) return batch_hip_fail((b), e_, #expr, __LINE__);    \
+    } while (0)
+
+bool life_rule(const gol_batch* b) {
+    return b->birth == GOL_RULE_LIFE_BIRTH && b->survive == GOL_RULE_LIFE_SURVIVE;
+}
+
+size_t plane_words(const gol_batch* b) { return (size_t)b->geo.boards * (size_t)b->geo.height; }
+
+// boards [first, first + count) inside the batch
+bool window_ok(const gol_batch* b, int64_t first, int64_t count) {
+    return first >= 0 && count >= 1 && first < b->geo.boards && count <= (int64_t)b->geo.boards - first;
+}
+
+void destroy_impl(gol_batch* b) {
+    hip_note(hipSetDevice(b->device), "batch destroy: hipSetDevice");
+    if (b->stream) hip_note(hipStreamSynchronize(b->stream), "batch destroy: hipStreamSynchronize");
+    for (void* p : {(void*)b->plane, (void*)b->prev, (void*)b->settled, (void*)b->series, (void*)b->hashes,
+                    (void*)b->hash_pops})
+        if (p) hip_note(hipFree(p), "batch destroy: hipFree");
+    if (b->stream) hip_note(hipStreamDestroy(b->stream), "batch destroy: hipStreamDestroy");
+    delete b;
+}
+
+}  // namespace
+
+extern "C" {
+
+int gol_batch_geometry_get(const gol_batch_config* cfg, gol_batch_geometry* out) {
+    if (!cfg || !out) return batch_err(nullptr, GOL_EINVAL, "gol_batch_geometry_get: null argument");
+    golbatch::Geometry g;
+    if (const char* why = golbatch::batch_geometry(*cfg, &g))
+        return batch_err(nullptr, GOL_EINVAL, "batch of %d boards %d x %d: %s", cfg->boards, cfg->width, cfg->height,
+                         why);
+    const golbatch::Lanes l = golbatch::batch_lanes(g.height, g.boards);
+    out->boards_per_wave = l.boards_per_wave;
+    out->waves = l.waves;
+    out->device_bytes = golbatch::batch_device_bytes(g);
+    return GOL_OK;
+}
+
+int gol_batch_create(gol_batch** out, const gol_batch_config* cfg) {
+    if (!out || !cfg) return batch_err(nullptr, GOL_EINVAL, "gol_batch_create: null argument");
+    *out = nullptr;
+    golbatch::Geometry g;
+    if (const char* why = golbatch::batch_geometry(*cfg, &g))
+        return batch_err(nullptr, GOL_EINVAL, "batch of %d boards %d x %d: %s", cfg->boards, cfg->width, cfg->height,
+                         why);
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
+        (void)hipGetLastError();
+        return batch_err(nullptr, GOL_ENODEV, "no HIP device available (libgol has no CPU fallback)");
+    }
+    if (cfg->device < 0 || cfg->device >= ndev)
+        return batch_err(nullptr, GOL_EINVAL, "device %d out of range (%d devices)", cfg->device, ndev);
+
+    gol_batch* b = new gol_batch();
+    b->geo = g;
+    b->lanes = golbatch::batch_lanes(g.height, g.boards);
+    b->birth = cfg->birth_mask;
+    b->survive = cfg->survive_mask;
+    b->device = cfg->device;
+    auto fail = [&](int rc, const char* what) {
+        (void)hipGetLastError();  // the failed call's status: reported through rc
+        destroy_impl(b);
+        return batch_err(nullptr, rc, "gol_batch_create: %s failed", what);
+    };
+    if (hipSetDevice(b->device) != hipSuccess) return fail(GOL_EHIP, "hipSetDevice");
+    const size_t bytes = plane_words(b) * sizeof(unsigned long long);
+    const size_t settle_bytes = (size_t)g.boards * sizeof(uint32_t);
+    if (hipMalloc(&b->plane, bytes) != hipSuccess || hipMalloc(&b->prev, bytes) != hipSuccess ||
+        hipMalloc(&b->settled, settle_bytes) != hipSuccess)
+        return fail(GOL_ENOMEM, "hipMalloc of the planes");
+    if (hipMemset(b->plane, 0, bytes) != hipSuccess || hipMemset(b->prev, 0, bytes) != hipSuccess ||
+        hipMemset(b->settled, 0, settle_bytes) != hipSuccess)
+        return fail(GOL_EHIP, "hipMemset");
+    if (hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking) != hipSuccess)
+        return fail(GOL_EHIP, "hipStreamCreateWithFlags");
+    if (hipDeviceSynchronize() != hipSuccess) return fail(GOL_EHIP, "hipDeviceSynchronize");
+    *out = b;
+    return GOL_OK;
+}
+
+void gol_batch_destroy(gol_batch* batch) {
+    if (batch) destroy_impl(batch);
+}
+
+const char* gol_batch_last_error(const gol_batch* batch) {
+    return batch ? batch->err.c_str() : gol_last_error(nullptr);
+}
+
+int gol_batch_seed(gol_batch* batch, uint64_t seed) {
+    if (!batch) return batch_err(nullptr, GOL_EINVAL, "gol_batch_seed: null handle");
+    BATCH_HIP(batch, hipSetDevice(batch->device));
+    BATCH_HIP(batch, golbatch::launch_batch_seed(batch->plane, (int64_t)plane_words(batch), batch->geo.width, seed,
+                                                 batch->stream));
+    BATCH_HIP(batch, hipStreamSynchronize(batch->stream));
+    batch->epoch = 0;
+    return GOL_OK;
+}
+
+int gol_batch_load(gol_batch* batch, int64_t first, int64_t count, const uint64_t* rows) {
+    if (!batch) return batch_err(nullptr, GOL_EINVAL, "gol_batch_load: null handle");
+    if (!rows) return batch_err(batch, GOL_EINVAL, "gol_batch_load: rows is null");
+    if (!window_ok(batch, first, count))
+        return batch_err(batch, GOL_EINVAL, "gol_batch_load: boards [%lld, %lld + %lld) outside the batch of %d",
+                         (long long)first, (long long)first, (long long)count, batch->geo.boards);
+    const size_t H = (size_t)batch->geo.height, n = (size_t)count * H;
+    const uint64_t wmask = batch->geo.width >= 64 ? ~0ull : (1ull << batch->geo.width) - 1ull;
+    std::vector<uint64_t> masked(n);  // bits at x >= width are ignored
+    for (size_t i = 0; i < n; ++i) masked[i] = rows[i] & wmask;
+    BATCH_HIP(batch, hipSetDevice(batch->device));
+    BATCH_HIP(batch, hipMemcpyAsync(batch->plane + (size_t)first * H, masked.data(), n * sizeof(uint64_t),
+                                    hipMemcpyHostToDevice, batch->stream));
+    BATCH_HIP(batch, hipStreamSynchronize(batch->stream));
+    batch->epoch = 0;
+    return GOL_OK;
+}
+
+int gol_batch_snapshot(gol_batch* batch, int64_t first, int64_t count, uint64_t* rows) {
+    if (!batch) return batch_err(nullptr, GOL_EINVAL, "gol_batch_snapshot: null handle");
+    if (!rows) return batch_err(batch, GOL_EINVAL, "gol_batch_snapshot: rows is null");
+    if (!window_ok(batch, first, count))
+        return batch_err(batch, GOL_EINVAL, "gol_batch_snapshot: boards [%lld, %lld + %lld) outside the batch of %d",
+                         (long long)first, (long long)first, (long long)count, batch->geo.boards);
+    const size_t H = (size_t)batch->geo.height;
+    BATCH_HIP(batch, hipSetDevice(batch->device));
+    // the plane never holds a bit at x >= width: every writer masks
+    BATCH_HIP(batch, hipMemcpyAsync(rows, batch->plane + (size_t)first * H, (size_t)count * H * sizeof(uint64_t),
+                                    hipMemcpyDeviceToHost, batch->stream));
+    BATCH_HIP(batch, hipStreamSynchronize(batch->stream));
+    return GOL_OK;
+}
+
+int gol_batch_step(gol_batch* batch, uint32_t generations, uint32_t* populations_out, size_t capacity,
+                   uint32_t* settled_out) {
+    if (!batch) return batch_err(nullptr, GOL_EINVAL, "gol_batch_step: null handle");
+    const size_t boards = (size_t)batch->geo.boards;
+    if (populations_out && capacity / boards < generations)  // boards * generations may pass 2^32: compare by division
+        return batch_err(batch, GOL_EINVAL, "gol_batch_step: populations_out holds %zu entries, %zu boards x %u "
+                         "generations need %zu", capacity, boards, generations, boards * (size_t)generations);
+    if (generations == 0) return GOL_OK;
+    const uint32_t chunk = std::min(batch->chunk ? batch->chunk : golbatch::kAutoChunk, generations);
+    BATCH_HIP(batch, hipSetDevice(batch->device));
+    if (populations_out && batch->series_gens < chunk) {
+        // nothing is in flight on the old buffer: every call synchronises
+        if (batch->series) BATCH_HIP(batch, hipFree(batch->series));
+        batch->series = nullptr;
+        batch->series_gens = 0;
+        const size_t bytes = boards * (size_t)chunk * sizeof(uint32_t);
+        if (hipMalloc(&batch->series, bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            batch->series = nullptr;
+            return batch_err(batch, GOL_ENOMEM, "gol_batch_step: hipMalloc of %zu bytes for the population series "
+                             "failed; nothing advanced", bytes);
+        }
+        batch->series_gens = chunk;
+    }
+    golbatch::StepParams p{};
+    p.plane = batch->plane;
+    p.prev = batch->prev;
+    p.pops = populations_out ? batch->series : nullptr;
+    p.settled = settled_out ? batch->settled : nullptr;
+    p.boards = batch->geo.boards;
+    p.width = batch->geo.width;
+    p.height = batch->geo.height;
+    p.boards_per_wave = batch->lanes.boards_per_wave;
+    p.vis_w = batch->geo.vis_w;
+    p.vis_h = batch->geo.vis_h;
+    p.pop_stride = (uint32_t)batch->series_gens;
+    p.birth = batch->birth;
+    p.survive = batch->survive;
+    for (uint32_t g0 = 0; g0 < generations; g0 += chunk) {
+        p.gens = std::min(chunk, generations - g0);
+        p.g0 = g0;
+        BATCH_HIP(batch, golbatch::launch_batch_step(p, life_rule(batch), batch->geo.clipped, batch->stream));
+        batch->epoch += p.gens;
+        if (populations_out)  // this launch's columns of the caller's [boards][generations]; waits for the launch
+            BATCH_HIP(batch, hipMemcpy2DAsync(populations_out + g0, (size_t)generations * sizeof(uint32_t), batch->series,
+                                              batch->series_gens * sizeof(uint32_t), (size_t)p.gens * sizeof(uint32_t),
+                                              boards, hipMemcpyDeviceToHost, batch->stream));
+    }
+    if (settled_out)
+        BATCH_HIP(batch, hipMemcpyAsync(settled_out, batch->settled, boards * sizeof(uint32_t), hipMemcpyDeviceToHost,
+                                        batch->stream));
+    BATCH_HIP(batch, hipStreamSynchronize(batch->stream));
+    return GOL_OK;
+}
+
+int gol_batch_hashes(gol_batch* batch, int64_t first, int64_t count, uint64_t* hashes_out,
+                     uint32_t* populations_out) {
+    if (!batch) return batch_err(nullptr, GOL_EINVAL, "gol_batch_hashes: null handle");
+    if (!hashes_out && !populations_out) return batch_err(batch, GOL_EINVAL, "gol_batch_hashes: both arrays are null");
+    if (!window_ok(batch, first, count))
+        return batch_err(batch, GOL_EINVAL, "gol_batch_hashes: boards [%lld, %lld + %lld) outside the batch of %d",
+                         (long long)first, (long long)first, (long long)count, batch->geo.boards);
+    BATCH_HIP(batch, hipSetDevice(batch->device));
+    const size_t n = (size_t)count;
+    if (batch->hashes_count < n) {
+        if (batch->hashes) BATCH_HIP(batch, hipFree(batch->hashes));
+        batch->hashes = nullptr;
+        if (batch->hash_pops) BATCH_HIP(batch, hipFree(batch->hash_pops));
+        batch->hash_pops = nullptr;
+        batch->hashes_count = 0;
+        if (hipMalloc(&batch->hashes, n * sizeof(unsigned long long)) != hipSuccess ||
+            hipMalloc(&batch->hash_pops, n * sizeof(uint32_t)) != hipSuccess) {
+            (void)hipGetLastError();
+            if (batch->hashes) hip_note(hipFree(batch->hashes), "gol_batch_hashes: hipFree");
+            batch->hashes = nullptr;
+            batch->hash_pops = nullptr;
+            return batch_err(batch, GOL_ENOMEM, "gol_batch_hashes: hipMalloc for %zu boards failed", n);
+        }
+        batch->hashes_count = n;
+    }
+    BATCH_HIP(batch, golbatch::launch_batch_hashes(batch->plane, batch->geo.height, first, count,
+                                                   hashes_out ? batch->hashes : nullptr,
+                                                   populations_out ? batch->hash_pops : nullptr, batch->stream));
+    if (hashes_out)
+        BATCH_HIP(batch, hipMemcpyAsync(hashes_out, batch->hashes, n * sizeof(uint64_t), hipMemcpyDeviceToHost,
+                                        batch->stream));
+    if (populations_out)
+        BATCH_HIP(batch, hipMemcpyAsync(populations_out, batch->hash_pops, n * sizeof(uint32_t), hipMemcpyDeviceToHost,
+                                        batch->stream));
+    BATCH_HIP(batch, hipStreamSynchronize(batch->stream));
+    return GOL_OK;
+}
+
+int gol_batch_epoch(const gol_batch* batch, uint64_t* epoch) {
+    if (!batch) return batch_err(nullptr, GOL_EINVAL, "gol_batch_epoch: null handle");
+    if (!epoch) return batch_err(const_cast<gol_batch*>(batch), GOL_EINVAL, "gol_batch_epoch: epoch is null");
+    *epoch = batch->epoch;
+    return GOL_OK;
+}
+
+int gol_batch_set_chunk(gol_batch* batch, uint32_t generations_per_launch) {
+    if (!batch) return batch_err(nullptr, GOL_EINVAL, "gol_batch_set_chunk: null handle");
+    batch->chunk = generations_per_launch;
+    return GOL_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,93 @@
+// gol_batch.h -- internal interface between the batch engine's C-ABI unit
+// (gol_batch.cpp) and its gfx950 kernels (gol_batch.hip); DESIGN.md section
+// 5f.  A header of its own: the step kernels' units include none of it.  Not
+// installed.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/gol.h"
+
+namespace golbatch {
+
+constexpr int kLanes = 64;              // CDNA wavefront: one 64-bit row per lane
+constexpr int kWavesPerWG = 4;          // 256-thread workgroups
+constexpr int32_t kMaxBoards = 1 << 22;
+constexpr uint32_t kAutoChunk = 1024;   // generations per launch (gol_batch_set_chunk 0): golc::kStepChunk
+
+// The lane mapping, a function of the geometry alone: a wave holds
+// k = 64 / height whole boards, lane l < k * height row l % height of the
+// wave's board l / height (the other lanes are idle); the last wave may hold
+// fewer boards.  What gol_batch_geometry_get reports and launch_batch_step
+// launches.
+struct Lanes {
+    int32_t boards_per_wave;
+    int64_t waves;
+};
+inline Lanes batch_lanes(int32_t height, int64_t boards) {
+    const int32_t k = kLanes / height;
+    return {k, (boards + k - 1) / k};
+}
+
+// The geometry a batch runs with, or the reason it is refused (null: fine).
+struct Geometry {
+    int32_t boards, width, height;
+    int32_t vis_w, vis_h;  // clipped: visible extents; torus: the board
+    bool clipped;
+};
+inline const char* batch_geometry(const gol_batch_config& c, Geometry* g) {
+    if (c.topology != GOL_TORUS && c.topology != GOL_REF_CLIPPED) return "unknown topology";
+    if (c.boards < 1 || c.boards > kMaxBoards) return "boards must be 1 .. 2^22";
+    if (c.width < 1 || c.height < 1 || c.width > kLanes || c.height > kLanes)
+        return "width and height must be 1 .. 64 stored cells";
+    if ((c.birth_mask | c.survive_mask) & ~0x1FFu) return "rule masks must fit in 9 bits";
+    const bool clipped = c.topology == GOL_REF_CLIPPED;
+    int32_t vw = c.width, vh = c.height;
+    if (clipped) {
+        // gol_create's refusal: the reference never completes a generation
+        // on a board where some cell has no visible neighbour
+        vw = c.vis_width > 0 ? c.vis_width : c.width - 1;
+        vh = c.vis_height > 0 ? c.vis_height : c.height - 1;
+        if (vw < 1 || vh < 1 || (vw == 1 && vh == 1) || c.width > vw + 1 || c.height > vh + 1)
+            return "ref-clipped board on which a cell has no visible neighbour: the reference never completes a "
+                   "generation on such a board (NextStateCellGathererActor.scala:26-27,39-58, "
+                   "CellActor.scala:75-76,92-94)";
+    } else if (c.width < 3 || c.height < 3) {
+        return "torus width and height must be 3 .. 64";
+    }
+    *g = {c.boards, c.width, c.height, vw, vh, clipped};
+    return nullptr;
+}
+
+// Device memory of a batch: the plane, the plane of the generation before it
+// (settle detection across launches) and one settle word per board.
+inline uint64_t batch_device_bytes(const Geometry& g) {
+    const uint64_t plane = (uint64_t)g.boards * (uint64_t)g.height * sizeof(uint64_t);
+    return 2 * plane + (uint64_t)g.boards * sizeof(uint32_t);
+}
+
+// One launch: `gens` generations of every board, in place.
+struct StepParams {
+    unsigned long long* plane;  // boards * height rows
+    unsigned long long* prev;   // settle: the plane one generation before `plane`; read when g0 > 0, always written
+    uint32_t* pops;             // populations: [boards][pop_stride], this launch's generations from column 0
+    uint32_t* settled;          // settle: [boards], 0 = not yet; read when g0 > 0, always written
+    int32_t boards, width, height, boards_per_wave;
+    int32_t vis_w, vis_h;
+    uint32_t gens;              // generations of this launch
+    uint32_t g0;                // generations of the call before this launch
+    uint32_t pop_stride;
+    uint32_t birth, survive;
+};
+
+// life: the B3/S23 instances; clipped: the topology; null pops / settled: the
+// instance without that part.  hipErrorInvalidValue for parameters outside
+// what the kernels index safely.
+hipError_t launch_batch_step(const StepParams& p, bool life, bool clipped, hipStream_t stream);
+hipError_t launch_batch_seed(unsigned long long* plane, int64_t words, int32_t width, uint64_t seed,
+                             hipStream_t stream);
+// hashes[i] / pops[i] (either may be null) of boards first .. first + count - 1.
+hipError_t launch_batch_hashes(const unsigned long long* plane, int32_t height, int64_t first, int64_t count,
+                               unsigned long long* hashes, uint32_t* pops, hipStream_t stream);
+
+}  // namespace golbatch

@@ -1,0 +1,303 @@
+// gol_batch.hip -- the batch engine's kernels (gol_batch_* in gol_batch.cpp;
+// DESIGN.md section 5f): many independent boards of at most 64 x 64 stored
+// cells, one 64-bit row per lane, k = 64 / height whole boards per wave.
+//
+// batch_step_kernel: one 8-byte load per lane, a run-time loop over the
+// launch's generations entirely in registers, one store (with settle
+// detection one more, the plane of the generation before).  No LDS traffic
+// but the cross-lane permutes, no scratch.  Per generation:
+//   vertical neighbours   torus, height 64: the DPP wave rotates;
+//                         torus, height < 64: ds_bpermute_b32 from source
+//                         lanes computed once (the board's own last / first
+//                         row at its seams);
+//                         clipped: the zero-filling DPP wave shifts of the
+//                         row masked to its visible cells, dead at the seams;
+//   horizontal neighbours shifts of the 64-bit column sums as two dwords; on
+//                         a torus bit width - 1 wraps to bit 0 and back; boards
+//                         of at most 32 columns run a loop without the upper dword;
+//   count and rule        gol_stencil.h's bit-sliced adders and rule circuits
+//                         (column sums first, as step_kernel);
+//   population (POP)      popcount of the lane's row, a DPP prefix sum over
+//                         the wave, one permute: the board's last lane
+//                         subtracts the prefix before its board and stores;
+//   settle (SETTLE)       the row against the row of two generations ago, a
+//                         ballot masked to the board's lanes.
+// Idle lanes (past k * height, or of boards past the batch) compute along --
+// the loop has no lane branch around a cross-lane operation, so DPP and
+// permutes see every lane -- and contribute to nothing: active lanes never read them (torus) or read them as
+// dead rows (clipped), and they neither store, sum nor vote.
+#include "gol_batch.h"
+#include "gol_stencil.h"
+
+namespace golbatch {
+
+using namespace gol::dev;
+
+namespace {
+
+struct Row {
+    uint32_t lo, hi;
+};
+__device__ __forceinline__ Row row_of(uint32_t lo, uint32_t hi) { return Row{lo, hi}; }
+
+constexpr int kDppRowShr = 0x110;     // row_shr:n = kDppRowShr + n (rows of 16 lanes)
+constexpr int kDppRowBcast15 = 0x142;  // lane 15 of each row -> the next row
+constexpr int kDppRowBcast31 = 0x143;  // lane 31 -> rows 2 and 3
+
+// v + (v of the DPP source lane, 0 where there is none or the row is masked out)
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ uint32_t dpp_add(uint32_t v) {
+    return v + (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, ROW_MASK, 0xf, false);
+}
+
+// Inclusive prefix sum over the wave's 64 lanes: four shifts inside the rows
+// of 16, then the two row broadcasts.
+__device__ __forceinline__ uint32_t wave_prefix_sum(uint32_t v) {
+    v = dpp_add<kDppRowShr + 1, 0xf>(v);
+    v = dpp_add<kDppRowShr + 2, 0xf>(v);
+    v = dpp_add<kDppRowShr + 4, 0xf>(v);
+    v = dpp_add<kDppRowShr + 8, 0xf>(v);
+    v = dpp_add<kDppRowBcast15, 0xa>(v);
+    v = dpp_add<kDppRowBcast31, 0xc>(v);
+    return v;
+}
+
+__device__ __forceinline__ uint32_t lane_read(int byte_addr, uint32_t v) {
+    return (uint32_t)__builtin_amdgcn_ds_bpermute(byte_addr, (int)v);
+}
+
+template <bool LIFE, bool CLIPPED, bool POP, bool SETTLE>
+__global__ __launch_bounds__(kLanes* kWavesPerWG) void batch_step_kernel(const StepParams p) {
+    const int lane = threadIdx.x & (kLanes - 1);
+    const int wave_in_wg = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / kLanes));
+    const int32_t wave = (int32_t)blockIdx.x * kWavesPerWG + wave_in_wg;  // waves <= boards <= 2^22
+    const int32_t board0 = wave * p.boards_per_wave;
+    if (board0 >= p.boards) return;  // the grid's last workgroup: wave-uniform, and nothing below synchronises
+    const int H = p.height;
+    const int bl = lane / H, y = lane - bl * H;
+    const int32_t board = board0 + bl;
+    const bool active = bl < p.boards_per_wave && board < p.boards;
+    const size_t idx = (size_t)board * (size_t)H + (size_t)y;  // active lanes: < boards * height
+
+    const unsigned long long wmask = p.width >= 64 ? ~0ull : (1ull << p.width) - 1ull;
+    const uint32_t wm_lo = (uint32_t)wmask, wm_hi = (uint32_t)(wmask >> 32);
+    // torus: bit width - 1 inside its dword (the lower one iff width <= 32: the NARROW loops below)
+    const uint32_t wsh = (uint32_t)(p.width - 1) & 31u;
+    // clipped: the lane's row as its neighbours see it, and whether it has a row above / below in its board
+    uint32_t sm_lo = 0xFFFFFFFFu, sm_hi = 0xFFFFFFFFu, upm = 0xFFFFFFFFu, dnm = 0xFFFFFFFFu;
+    if constexpr (CLIPPED) {
+        const unsigned long long vmask = p.vis_w >= 64 ? ~0ull : (1ull << p.vis_w) - 1ull;
+        const bool seen = active && y < p.vis_h;
+        sm_lo = seen ? (uint32_t)vmask : 0u;
+        sm_hi = seen ? (uint32_t)(vmask >> 32) : 0u;
+        upm = y > 0 ? 0xFFFFFFFFu : 0u;
+        dnm = y < H - 1 ? 0xFFFFFFFFu : 0u;
+    }
+    // torus, height < 64: the lanes holding the rows above and below, inside the lane's own board
+    const int up_addr = 4 * (active ? (y > 0 ? lane - 1 : lane + H - 1) : lane);
+    const int dn_addr = 4 * (active ? (y < H - 1 ? lane + 1 : lane - (H - 1)) : lane);
+    // population: the board's last lane stores; the prefix before the board is the one of the lane before its
+    // first (none before lane 0)
+    const bool writer = active && y == H - 1;
+    const int first_lane = lane - (H - 1);
+    const int before_addr = 4 * (writer && first_lane > 0 ? first_lane - 1 : lane);
+    const bool has_before = writer && first_lane > 0;
+    // settle: the board's lanes in a ballot
+    unsigned long long bm = ~0ull;
+    if constexpr (SETTLE) {
+        const unsigned long long hm = H >= 64 ? ~0ull : (1ull << H) - 1ull;
+        bm = active ? hm << (bl * H) : ~0ull;
+    }
+
+    Row cur = {0u, 0u}, prev = {0u, 0u};
+    uint32_t first = 0u;
+    if (active) {
+        const unsigned long long r = p.plane[idx];
+        cur = {(uint32_t)r, (uint32_t)(r >> 32)};
+        if constexpr (SETTLE) {
+            if (p.g0 > 0) {
+                const unsigned long long q = p.prev[idx];
+                prev = {(uint32_t)q, (uint32_t)(q >> 32)};
+                first = p.settled[board];
+            }
+        }
+    }
+
+    // ROT: the wave is one torus board of 64 rows.  NARROW: width <= 32 -- a row's upper dword is zero and stays
+    // zero, so nothing is computed for it (the reference's 8 x 8 board: half the instructions).
+    auto run = [&](auto ROT_, auto NARROW_) __attribute__((always_inline)) {
+        constexpr bool ROT = decltype(ROT_)::value;
+        constexpr bool NARROW = decltype(NARROW_)::value;
+        if constexpr (NARROW) cur.hi = prev.hi = 0u;
+        for (uint32_t g = 0; g < p.gens; ++g) {
+            // rows above (a) and below (b); s: the centre as a neighbour sees it
+            Row a = {0u, 0u}, b = {0u, 0u}, s = cur;
+            if constexpr (CLIPPED) {
+                s = {cur.lo & sm_lo, NARROW ? 0u : cur.hi & sm_hi};
+                a.lo = dpp_shr1_zero(s.lo) & upm;
+                b.lo = dpp_shl1_zero(s.lo) & dnm;
+                if constexpr (!NARROW) {
+                    a.hi = dpp_shr1_zero(s.hi) & upm;
+                    b.hi = dpp_shl1_zero(s.hi) & dnm;
+                }
+            } else if constexpr (ROT) {
+                a.lo = dpp_ror1(cur.lo);
+                b.lo = dpp_rol1(cur.lo);
+                if constexpr (!NARROW) {
+                    a.hi = dpp_ror1(cur.hi);
+                    b.hi = dpp_rol1(cur.hi);
+                }
+            } else {
+                a.lo = lane_read(up_addr, cur.lo);
+                b.lo = lane_read(dn_addr, cur.lo);
+                if constexpr (!NARROW) {
+                    a.hi = lane_read(up_addr, cur.hi);
+                    b.hi = lane_read(dn_addr, cur.hi);
+                }
+            }
+            // column sums (v1 v0) = a + s + b, and their copies from the columns west and east
+            const Row v0 = row_of(GOL_BITOP3(a.lo, s.lo, b.lo, kXor3), NARROW ? 0u : GOL_BITOP3(a.hi, s.hi, b.hi, kXor3));
+            const Row v1 = row_of(GOL_BITOP3(a.lo, s.lo, b.lo, kMaj), NARROW ? 0u : GOL_BITOP3(a.hi, s.hi, b.hi, kMaj));
+            auto west = [&](const Row& v) -> Row {  // column x - 1 at bit x
+                Row w = row_of(v.lo << 1, NARROW ? 0u : __builtin_amdgcn_alignbit(v.hi, v.lo, 31));
+                if constexpr (!CLIPPED) w.lo |= ((NARROW ? v.lo : v.hi) >> wsh) & 1u;
+                return w;
+            };
+            auto east = [&](const Row& v) -> Row {  // column x + 1 at bit x
+                Row e = row_of(NARROW ? v.lo >> 1 : __builtin_amdgcn_alignbit(v.hi, v.lo, 1), v.hi >> 1);
+                if constexpr (!CLIPPED) {
+                    const uint32_t t = (v.lo & 1u) << wsh;
+                    if constexpr (NARROW) e.lo |= t;
+                    else e.hi |= t;
+                }
+                return e;
+            };
+            const Row w0 = west(v0), w1 = west(v1), e0 = east(v0), e1 = east(v1);
+            Row nx = {0u, 0u};
+            if constexpr (LIFE && !CLIPPED) {
+                nx.lo = rule_b3s23_fullsum(w0.lo, w1.lo, v0.lo, v1.lo, e0.lo, e1.lo, cur.lo);
+                if constexpr (!NARROW) nx.hi = rule_b3s23_fullsum(w0.hi, w1.hi, v0.hi, v1.hi, e0.hi, e1.hi, cur.hi);
+            } else {
+                auto half = [&](uint32_t aw, uint32_t bw, uint32_t ww0, uint32_t ww1, uint32_t ee0, uint32_t ee1,
+                                uint32_t al) -> uint32_t {
+                    const uint32_t p0 = aw ^ bw, p1 = aw & bw;  // the column minus its centre
+                    const uint32_t nb0 = GOL_BITOP3(ww0, ee0, p0, kXor3);
+                    const uint32_t c0 = GOL_BITOP3(ww0, ee0, p0, kMaj);
+                    const uint32_t pp = GOL_BITOP3(ww1, ee1, p1, kXor3);
+                    const uint32_t qq = GOL_BITOP3(ww1, ee1, p1, kMaj);
+                    uint32_t o;
+                    GOL_RULE_FROM_COUNT(o, LIFE, p, nb0, c0, pp, qq, al);
+                    return o;
+                };
+                nx.lo = half(a.lo, b.lo, w0.lo, w1.lo, e0.lo, e1.lo, cur.lo);
+                if constexpr (!NARROW) nx.hi = half(a.hi, b.hi, w0.hi, w1.hi, e0.hi, e1.hi, cur.hi);
+            }
+            nx.lo &= wm_lo;
+            if constexpr (!NARROW) nx.hi &= wm_hi;
+
+            if constexpr (POP) {
+                const uint32_t bits = (uint32_t)__builtin_popcount(nx.lo) + (NARROW ? 0u : (uint32_t)__builtin_popcount(nx.hi));
+                const uint32_t incl = wave_prefix_sum(active ? bits : 0u);
+                const uint32_t before = lane_read(before_addr, incl);
+                if (writer) p.pops[(size_t)board * p.pop_stride + g] = incl - (has_before ? before : 0u);
+            }
+            if constexpr (SETTLE) {
+                const unsigned long long same = __ballot(nx.lo == prev.lo && (NARROW || nx.hi == prev.hi));
+                const uint32_t gen = p.g0 + g + 1u;  // generation of the call that nx is
+                if (gen >= 2u && first == 0u && (same & bm) == bm) first = gen;
+                prev = cur;
+            }
+            cur = nx;
+        }
+    };
+    // wave-uniform, outside the loop
+    const bool rot = !CLIPPED && H == kLanes, narrow = p.width <= 32;
+    if (rot && narrow) run(std::true_type{}, std::true_type{});
+    else if (rot) run(std::true_type{}, std::false_type{});
+    else if (narrow) run(std::false_type{}, std::true_type{});
+    else run(std::false_type{}, std::false_type{});
+
+    if (active) {
+        p.plane[idx] = (unsigned long long)cur.lo | ((unsigned long long)cur.hi << 32);
+        if constexpr (SETTLE) {
+            p.prev[idx] = (unsigned long long)prev.lo | ((unsigned long long)prev.hi << 32);
+            if (y == 0) p.settled[board] = first;
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void batch_seed_kernel(unsigned long long* plane, int64_t words,
+                                                          unsigned long long wmask, unsigned long long seed) {
+    const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (k >= words) return;
+    unsigned long long z = seed + 0x9E3779B97F4A7C15ull * ((unsigned long long)k + 1ull);
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    z ^= z >> 31;
+    plane[k] = z & wmask;
+}
+
+// One thread per board: the state hash of include/gol.h with row0 = 0 and the
+// one column group 0 -- E the row's even columns, O its odd ones -- and the
+// population.  Off the step's path: a board's rows are read by one lane.
+__global__ __launch_bounds__(256) void batch_hash_kernel(const unsigned long long* plane, int32_t height,
+                                                          int64_t first, int64_t count, unsigned long long* hashes,
+                                                          uint32_t* pops) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= count) return;
+    const unsigned long long* rows = plane + (size_t)(first + i) * (size_t)height;
+    unsigned long long h = 0ull;
+    uint32_t n = 0u;
+    for (int y = 0; y < height; ++y) {
+        const unsigned long long r = rows[y];
+        const uint32_t u0 = unzip_bits((uint32_t)r), u1 = unzip_bits((uint32_t)(r >> 32));
+        const uint32_t e = (u0 & 0xFFFFu) | (u1 << 16), o = (u0 >> 16) | (u1 & 0xFFFF0000u);
+        const uint32_t ae = gol::hash_row_key(y);
+        h += (unsigned long long)e * ae + (unsigned long long)o * (uint32_t)(ae + gol::kHashOddAdd);
+        n += (uint32_t)__builtin_popcountll(r);
+    }
+    if (hashes) hashes[i] = h * (unsigned long long)gol::hash_pair_key(0u);
+    if (pops) pops[i] = n;
+}
+
+template <bool LIFE, bool CLIPPED>
+hipError_t launch_step_flags(const StepParams& p, dim3 grid, hipStream_t stream) {
+    const dim3 block(kLanes * kWavesPerWG);
+    const bool pop = p.pops != nullptr, settle = p.settled != nullptr;
+    if (pop && settle) return gol::launch_kernel(batch_step_kernel<LIFE, CLIPPED, true, true>, grid, block, stream, p);
+    if (pop) return gol::launch_kernel(batch_step_kernel<LIFE, CLIPPED, true, false>, grid, block, stream, p);
+    if (settle) return gol::launch_kernel(batch_step_kernel<LIFE, CLIPPED, false, true>, grid, block, stream, p);
+    return gol::launch_kernel(batch_step_kernel<LIFE, CLIPPED, false, false>, grid, block, stream, p);
+}
+
+}  // namespace
+
+hipError_t launch_batch_step(const StepParams& p, bool life, bool clipped, hipStream_t stream) {
+    // every index the kernel forms stays inside the plane, the series and the settle words
+    if (!p.plane || p.boards < 1 || p.boards > kMaxBoards || p.width < 1 || p.width > kLanes || p.height < 1 ||
+        p.height > kLanes || p.boards_per_wave != batch_lanes(p.height, p.boards).boards_per_wave || p.gens < 1 ||
+        (p.pops && p.pop_stride < p.gens) || (p.settled && !p.prev) || (clipped && (p.vis_w < 1 || p.vis_h < 1)))
+        return hipErrorInvalidValue;
+    const int64_t waves = batch_lanes(p.height, p.boards).waves;
+    const dim3 grid((unsigned)((waves + kWavesPerWG - 1) / kWavesPerWG));
+    if (life) return clipped ? launch_step_flags<true, true>(p, grid, stream) : launch_step_flags<true, false>(p, grid, stream);
+    return clipped ? launch_step_flags<false, true>(p, grid, stream) : launch_step_flags<false, false>(p, grid, stream);
+}
+
+hipError_t launch_batch_seed(unsigned long long* plane, int64_t words, int32_t width, uint64_t seed,
+                             hipStream_t stream) {
+    if (!plane || words < 1 || width < 1 || width > kLanes) return hipErrorInvalidValue;
+    const unsigned long long wmask = width >= 64 ? ~0ull : (1ull << width) - 1ull;
+    return gol::launch_kernel(batch_seed_kernel, dim3((unsigned)((words + 255) / 256)), dim3(256), stream, plane, words,
+                              wmask, (unsigned long long)seed);
+}
+
+hipError_t launch_batch_hashes(const unsigned long long* plane, int32_t height, int64_t first, int64_t count,
+                               unsigned long long* hashes, uint32_t* pops, hipStream_t stream) {
+    if (!plane || height < 1 || height > kLanes || first < 0 || count < 1 || (!hashes && !pops))
+        return hipErrorInvalidValue;
+    return gol::launch_kernel(batch_hash_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), stream, plane, height,
+                              first, count, hashes, pops);
+}
+
+}  // namespace golbatch

@@ -115,6 +115,28 @@ class GolActiveStats(ctypes.Structure):
     ]
 
 
+class GolBatchConfig(ctypes.Structure):
+    _fields_ = [
+        ("boards", ctypes.c_int32),
+        ("width", ctypes.c_int32),
+        ("height", ctypes.c_int32),
+        ("topology", ctypes.c_int32),
+        ("birth_mask", ctypes.c_uint32),
+        ("survive_mask", ctypes.c_uint32),
+        ("device", ctypes.c_int32),
+        ("vis_width", ctypes.c_int32),
+        ("vis_height", ctypes.c_int32),
+    ]
+
+
+class GolBatchGeometry(ctypes.Structure):
+    _fields_ = [
+        ("boards_per_wave", ctypes.c_int32),
+        ("waves", ctypes.c_int64),
+        ("device_bytes", ctypes.c_uint64),
+    ]
+
+
 # gol_write_region modes (include/gol.h GOL_REGION_*)
 GOL_REGION_COPY = 0
 GOL_REGION_OR = 1
@@ -193,6 +215,17 @@ _SIGNATURES = {
     "gol_set_active_rows": (_c.c_int, [_vp, _c.c_int32]),
     "gol_active_stats_read": (_c.c_int, [_vp, ctypes.POINTER(GolActiveStats), _c.c_int32]),
     "gol_active_rows": (_c.c_int, [_vp, ctypes.POINTER(_c.c_int64), _c.c_int32, ctypes.POINTER(_c.c_int32)]),
+    "gol_batch_geometry_get": (_c.c_int, [ctypes.POINTER(GolBatchConfig), ctypes.POINTER(GolBatchGeometry)]),
+    "gol_batch_create": (_c.c_int, [ctypes.POINTER(_vp), ctypes.POINTER(GolBatchConfig)]),
+    "gol_batch_destroy": (None, [_vp]),
+    "gol_batch_last_error": (_c.c_char_p, [_vp]),
+    "gol_batch_seed": (_c.c_int, [_vp, _c.c_uint64]),
+    "gol_batch_load": (_c.c_int, [_vp, _c.c_int64, _c.c_int64, _u64p]),
+    "gol_batch_snapshot": (_c.c_int, [_vp, _c.c_int64, _c.c_int64, _u64p]),
+    "gol_batch_step": (_c.c_int, [_vp, _c.c_uint32, _u32p, _c.c_size_t, _u32p]),
+    "gol_batch_hashes": (_c.c_int, [_vp, _c.c_int64, _c.c_int64, _u64p, _u32p]),
+    "gol_batch_epoch": (_c.c_int, [_vp, _u64p]),
+    "gol_batch_set_chunk": (_c.c_int, [_vp, _c.c_uint32]),
 }
 
 
@@ -222,6 +255,13 @@ def _strerror(code: int) -> str:
 def check(code: int, ctx=None) -> None:
     if code != GOL_OK:
         msg = lib.gol_last_error(ctx)
+        raise GolError(code, msg.decode() if msg else "")
+
+
+def check_batch(code: int, batch=None) -> None:
+    """check() for the batch engine's calls (gol_batch_last_error)."""
+    if code != GOL_OK:
+        msg = lib.gol_batch_last_error(batch)
         raise GolError(code, msg.decode() if msg else "")
 
 

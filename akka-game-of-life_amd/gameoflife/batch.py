@@ -1,0 +1,144 @@
+"""Batch engine: many independent small boards stepped by one launch.
+
+Where the reference runs one BoardCreator -- one actor system -- per board
+(BoardCreator.scala:18-23), a ``GolBatch`` holds ``boards`` boards of one
+geometry and rule, each at most 64 x 64 stored cells, and advances all of
+them per launch through libgol's gol_batch_* entry points: random soups until
+they settle, one pattern under many perturbations, or many copies of the
+reference's own 7 x 7 board.  A board's row is one uint64 (bit x = cell x).
+"""
+from __future__ import annotations
+
+import ctypes
+
+import numpy as np
+
+from . import _native as N
+from .rules import Rule, rule_by_name
+
+
+class GolBatch:
+    """A batch of boards on one GPU (gol_batch_create .. gol_batch_destroy)."""
+
+    def __init__(self, boards: int, width: int, height: int, *, topology: str = "torus",
+                 rule: Rule | str = "life", vis: tuple[int, int] | None = None, device: int = 0):
+        self.rule = rule_by_name(rule) if isinstance(rule, str) else rule
+        self.topology = topology
+        cfg = N.GolBatchConfig()
+        cfg.boards, cfg.width, cfg.height = boards, width, height
+        cfg.topology = {"torus": N.GOL_TORUS, "ref-clipped": N.GOL_REF_CLIPPED}[topology]
+        cfg.birth_mask, cfg.survive_mask = self.rule.birth, self.rule.survive
+        cfg.device = device
+        cfg.vis_width, cfg.vis_height = vis if vis is not None else (0, 0)
+        self._cfg = cfg
+        h = ctypes.c_void_p()
+        N.check_batch(N.lib.gol_batch_create(ctypes.byref(h), ctypes.byref(cfg)))
+        self._h = h
+        self.boards, self.width, self.height = boards, width, height
+        self.device = device
+
+    # -- lifecycle ---------------------------------------------------------
+    def close(self) -> None:
+        if getattr(self, "_h", None) is not None and self._h.value:
+            N.lib.gol_batch_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _chk(self, rc: int) -> None:
+        N.check_batch(rc, self._h)
+
+    def geometry(self) -> dict:
+        """The lane mapping: boards per 64-lane wave, waves, device bytes."""
+        g = N.GolBatchGeometry()
+        N.check_batch(N.lib.gol_batch_geometry_get(ctypes.byref(self._cfg), ctypes.byref(g)))
+        return {"boards_per_wave": g.boards_per_wave, "waves": g.waves, "device_bytes": g.device_bytes}
+
+    # -- state -------------------------------------------------------------
+    def seed(self, seed: int = 0x5EED) -> None:
+        self._chk(N.lib.gol_batch_seed(self._h, seed))
+
+    def load(self, x, first: int = 0) -> None:
+        """Boards first .. first + n - 1 from uint64 [n][H] rows or uint8
+        [n][H][W] cells; resets the epoch."""
+        a = np.asarray(x)
+        if a.ndim == 3:
+            a = pack_rows(a)
+        a = np.ascontiguousarray(a, dtype=np.uint64)
+        if a.ndim != 2 or a.shape[1] != self.height:
+            raise ValueError(f"boards must be uint64 [n][{self.height}] rows or uint8 [n][{self.height}]"
+                             f"[{self.width}] cells, not {a.shape}")
+        self._chk(N.lib.gol_batch_load(self._h, first, a.shape[0], a.ctypes.data_as(N._u64p)))
+
+    def snapshot(self, first: int = 0, count: int | None = None) -> np.ndarray:
+        """uint64 [n][H] rows of boards first .. first + count - 1."""
+        count = self.boards - first if count is None else count
+        out = np.zeros((max(count, 0), self.height), dtype=np.uint64)
+        self._chk(N.lib.gol_batch_snapshot(self._h, first, count, out.ctypes.data_as(N._u64p)))
+        return out
+
+    def cells(self, first: int = 0, count: int | None = None) -> np.ndarray:
+        """uint8 [n][H][W] cells of boards first .. first + count - 1."""
+        return unpack_rows(self.snapshot(first, count), self.width)
+
+    def step(self, generations: int = 1, populations: bool = False, settled: bool = False):
+        """Advance every board.  populations=True: uint32 [boards][generations],
+        the live stored cells of each board after each generation; settled=True:
+        uint32 [boards], the first generation g >= 2 of this call at which the
+        board equals itself two generations earlier (0: none).  Returns the one
+        asked for, (populations, settled) for both, else None."""
+        pop = np.zeros((self.boards, generations), dtype=np.uint32) if populations else None
+        st = np.zeros(self.boards, dtype=np.uint32) if settled else None
+        self._chk(N.lib.gol_batch_step(self._h, generations, pop.ctypes.data_as(N._u32p) if populations else None,
+                                       pop.size if populations else 0,
+                                       st.ctypes.data_as(N._u32p) if settled else None))
+        if populations and settled:
+            return pop, st
+        return pop if populations else st
+
+    def hashes(self) -> np.ndarray:
+        """Each board's state hash (what GolEngine.hash() gives for the same cells)."""
+        out = np.zeros(self.boards, dtype=np.uint64)
+        self._chk(N.lib.gol_batch_hashes(self._h, 0, self.boards, out.ctypes.data_as(N._u64p), None))
+        return out
+
+    def populations(self) -> np.ndarray:
+        """Each board's live stored cells."""
+        out = np.zeros(self.boards, dtype=np.uint32)
+        self._chk(N.lib.gol_batch_hashes(self._h, 0, self.boards, None, out.ctypes.data_as(N._u32p)))
+        return out
+
+    @property
+    def epoch(self) -> int:
+        e = ctypes.c_uint64(0)
+        self._chk(N.lib.gol_batch_epoch(self._h, ctypes.byref(e)))
+        return e.value
+
+    def set_chunk(self, n: int) -> None:
+        """Generations per launch (0: automatic); results never depend on it."""
+        self._chk(N.lib.gol_batch_set_chunk(self._h, n))
+
+
+def pack_rows(cells) -> np.ndarray:
+    """uint8 [n][H][W] cells (W <= 64) -> uint64 [n][H] rows, bit x = cell x."""
+    c = np.asarray(cells)
+    if c.ndim != 3 or c.shape[2] > 64:
+        raise ValueError(f"cells must be [n][H][W] with W <= 64, not {c.shape}")
+    weights = np.uint64(1) << np.arange(c.shape[2], dtype=np.uint64)
+    return ((c != 0).astype(np.uint64) * weights).sum(axis=2, dtype=np.uint64)
+
+
+def unpack_rows(rows, width: int) -> np.ndarray:
+    """uint64 [n][H] rows -> uint8 [n][H][width] cells."""
+    r = np.asarray(rows, dtype=np.uint64)
+    return ((r[:, :, None] >> np.arange(width, dtype=np.uint64)) & np.uint64(1)).astype(np.uint8)

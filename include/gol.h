@@ -56,7 +56,10 @@ extern "C" {
  * version: additive entry points change nothing a version-2 caller relies on.
  * So were gol_set_active_rows, gol_active_stats_read and gol_active_rows, and
  * gol_step_series and gol_group_step_series (the fused population series),
- * and gol_find (the pattern search). */
+ * and gol_find (the pattern search), and the batch engine with a handle type
+ * of its own (gol_batch_geometry_get, gol_batch_create, gol_batch_destroy,
+ * gol_batch_last_error, gol_batch_seed, gol_batch_load, gol_batch_snapshot,
+ * gol_batch_step, gol_batch_hashes, gol_batch_epoch, gol_batch_set_chunk). */
 #define GOL_ABI_VERSION 2
 
 /* Return codes. */
@@ -482,6 +485,106 @@ int gol_group_step_series(gol_group* group, uint32_t generations, uint64_t* hash
 int gol_group_sync(gol_group* group);
 const char* gol_group_last_error(const gol_group* group);
 void gol_group_destroy(gol_group* group);
+
+/* Batches of small boards: `boards` independent boards
+ * of one geometry and rule, each at most 64 x 64 stored cells, stepped by one
+ * launch; a board stays in registers for a whole launch, one 64-bit row per
+ * lane.  Replaces running one BoardCreator (BoardCreator.scala:18-23, one
+ * actor system per board) per soup: the reference's own default board (7 x 7
+ * cells, stored 8 x 8; application.conf:32-33) is one eighth of a wave.  A
+ * handle type of its own next to gol_ctx: a batch shares nothing with a
+ * context, is not sharded, and owns its device memory on one GPU; the
+ * conventions above (return codes, any OS thread, no CPU fallback) hold, with
+ * gol_batch_last_error in gol_last_error's place (NULL: the process-wide last
+ * error, e.g. of a failed gol_batch_create).
+ *
+ * Host buffers: row y of board i is one uint64_t at rows[(i - first) * height
+ * + y], bit x = cell x; bits at x >= width are ignored on load and zero on
+ * snapshot.  The device plane has the same layout.
+ *
+ * Geometry.  GOL_TORUS: 3 <= width, height <= 64, any value (a row is one
+ * register and wraps with two shifts: not gol_config's multiple-of-32 rule).
+ * GOL_REF_CLIPPED: width / height / vis_* mean what they mean in gol_config,
+ * stored extents 1 .. 64; the boards gol_create refuses (a cell with no
+ * visible neighbour) are refused alike.  1 <= boards <= 2^22; 9-bit rule
+ * masks.  Anything else is GOL_EINVAL with a message.  The rule is evaluated
+ * exactly as gol_step evaluates it on the same topology: every stored cell is
+ * updated from its visible neighbours.
+ *
+ * A wave of 64 lanes holds boards_per_wave = 64 / height whole boards, lane l
+ * row l % height of its board l / height; waves = ceil(boards /
+ * boards_per_wave); device_bytes is what gol_batch_create allocates (the
+ * plane, the plane of the generation before it that settle detection carries
+ * between launches, and the settle words).  gol_batch_geometry_get validates
+ * as gol_batch_create does and needs no device. */
+typedef struct gol_batch gol_batch;
+typedef struct gol_batch_config {
+    int32_t boards;                  /* >= 1 */
+    int32_t width, height;           /* stored cells per board, each <= 64 */
+    int32_t topology;                /* GOL_TORUS or GOL_REF_CLIPPED */
+    uint32_t birth_mask, survive_mask;
+    int32_t device;
+    int32_t vis_width, vis_height;   /* REF_CLIPPED: as gol_config (0 => width-1 / height-1) */
+} gol_batch_config;
+typedef struct gol_batch_geometry {
+    int32_t boards_per_wave;
+    int64_t waves;
+    uint64_t device_bytes;
+} gol_batch_geometry;
+int gol_batch_geometry_get(const gol_batch_config* cfg, gol_batch_geometry* out);
+
+/* Create a batch, every board dead at epoch 0 (GOL_ENODEV without a HIP
+ * device, after the geometry has been validated); free it with
+ * gol_batch_destroy (NULL: nothing happens). */
+int gol_batch_create(gol_batch** out, const gol_batch_config* cfg);
+void gol_batch_destroy(gol_batch* batch);
+const char* gol_batch_last_error(const gol_batch* batch);
+
+/* Seed every board: row y of board i is the splitmix64 output of counter
+ * k = i * height + y -- z = seed + 0x9E3779B97F4A7C15 (k + 1), then
+ * z = (z ^ (z >> 30)) 0xBF58476D1CE4E5B9, z = (z ^ (z >> 27))
+ * 0x94D049BB133111EB, z ^= z >> 31 (mod 2^64) -- the low `width` bits of z.
+ * Resets the epoch to 0. */
+int gol_batch_seed(gol_batch* batch, uint64_t seed);
+
+/* Load / read boards [first, first + count), count >= 1, in the host layout
+ * above.  gol_batch_load resets the epoch to 0 (the boards it does not name
+ * keep their cells).  Both synchronise. */
+int gol_batch_load(gol_batch* batch, int64_t first, int64_t count, const uint64_t* rows);
+int gol_batch_snapshot(gol_batch* batch, int64_t first, int64_t count, uint64_t* rows);
+
+/* Advance every board `generations` generations; synchronises.
+ * populations_out (nullable): [boards][generations] -- entry
+ * [i * generations + g] is the number of live stored cells of board i after
+ * generation g + 1 of the call; `capacity` is its size in entries.
+ * settled_out (nullable): [boards] -- the smallest g in 2 .. generations such
+ * that board i after g generations of this call equals board i after g - 2
+ * (g = 2 compares with the board the call started from), 0 if there is none:
+ * still lifes and period-2 ash.  Per call on purpose: it needs nothing from
+ * earlier calls.  generations = 0 is GOL_OK and writes nothing.  The device
+ * series buffer belongs to the handle and grows on demand (GOL_ENOMEM, and
+ * nothing advanced, if it cannot).  GOL_EINVAL, nothing advanced and nothing
+ * written, for a NULL handle or populations_out with capacity < boards *
+ * generations. */
+int gol_batch_step(gol_batch* batch, uint32_t generations, uint32_t* populations_out, size_t capacity,
+                   uint32_t* settled_out);
+
+/* State hash (the header comment's definition with row0 = 0 and the one
+ * column group g = 0: what gol_hash returns for a context holding the same
+ * cells) and population of boards [first, first + count).  Either array may be
+ * NULL, not both.  Synchronises; changes nothing. */
+int gol_batch_hashes(gol_batch* batch, int64_t first, int64_t count, uint64_t* hashes_out,
+                     uint32_t* populations_out);
+
+/* Generations every board has advanced since the last seed / load. */
+int gol_batch_epoch(const gol_batch* batch, uint64_t* epoch);
+
+/* Knob (results, settled_out included, never depend on it): a launch runs at
+ * most this many generations, and the boards pass through HBM between
+ * launches -- with settle detection on, the plane of the generation before
+ * too -- so no single launch is long whatever a caller asks for.  0 = the
+ * automatic value, 1024 (the chunk gol_step plans in). */
+int gol_batch_set_chunk(gol_batch* batch, uint32_t generations_per_launch);
 
 /* Kernel timing: when enabled, the dominant step-kernel launch of every pass
  * (the whole shard, or a sharded shard's interior rows) is bracketed by HIP
