@@ -1,8 +1,9 @@
-// gol_batch.cpp -- C ABI of the batch engine (include/gol.h gol_batch_*;
-// DESIGN.md section 5f): many independent boards of at most 64 x 64 stored
-// cells stepped by one launch (kernels: gol_batch.hip).  A handle type of its
-// own: it shares the error conventions and the HIP status discipline with the
-// contexts (gol_ctx.h), and nothing else -- no planner, no step kernel.
+// gol_batch.cpp -- C ABI of the batch engine (include/gol.h gol_batch_* and
+// gol_cycle_*; DESIGN.md sections 5f and 5g): many independent boards of at
+// most 64 x 64 stored cells stepped by one launch (kernels: gol_batch.hip).  A
+// handle type of its own: it shares the error conventions and the HIP status
+// discipline with the contexts (gol_ctx.h), and nothing else -- no planner, no
+// step kernel.
 #include <algorithm>
 #include <cstdarg>
 #include <cstdio>
@@ -21,8 +22,15 @@ struct gol_batch {
     uint64_t epoch = 0;
     hipStream_t stream = nullptr;
     unsigned long long* plane = nullptr;  // boards * height rows
-    unsigned long long* prev = nullptr;   // the plane one generation before (settle detection across launches)
+    // the plane one generation before (settle detection across launches), or a cycle call's snapshot plane: a call
+    // is one or the other, and neither reads what an earlier call left in it
+    unsigned long long* prev = nullptr;
     uint32_t* settled = nullptr;          // [boards]
+    // gol_cycle_step's words, allocated by its first call: period [boards], seen [boards], then the two counters
+    // (boards that have a period, the largest period)
+    uint32_t* cycle_words = nullptr;
+    uint64_t cycle_launches = 0, cycle_boards = 0;  // gol_cycle_stats: the last gol_cycle_step call
+    uint32_t cycle_max_period = 0;
     // the series of one launch, [boards][series_gens] (grown on demand), and gol_batch_hashes' results
     uint32_t* series = nullptr;
     size_t series_gens = 0;
@@ -77,7 +85,7 @@ void destroy_impl(gol_batch* b) {
     hip_note(hipSetDevice(b->device), "batch destroy: hipSetDevice");
     if (b->stream) hip_note(hipStreamSynchronize(b->stream), "batch destroy: hipStreamSynchronize");
     for (void* p : {(void*)b->plane, (void*)b->prev, (void*)b->settled, (void*)b->series, (void*)b->hashes,
-                    (void*)b->hash_pops})
+                    (void*)b->hash_pops, (void*)b->cycle_words})
         if (p) hip_note(hipFree(p), "batch destroy: hipFree");
     if (b->stream) hip_note(hipStreamDestroy(b->stream), "batch destroy: hipStreamDestroy");
     delete b;
@@ -245,6 +253,79 @@ int gol_batch_step(gol_batch* batch, uint32_t generations, uint32_t* populations
         BATCH_HIP(batch, hipMemcpyAsync(settled_out, batch->settled, boards * sizeof(uint32_t), hipMemcpyDeviceToHost,
                                         batch->stream));
     BATCH_HIP(batch, hipStreamSynchronize(batch->stream));
+    return GOL_OK;
+}
+
+int gol_cycle_snapshot_generation(uint32_t generation, uint32_t* snapshot_out) {
+    if (generation == 0 || !snapshot_out)
+        return batch_err(nullptr, GOL_EINVAL, "gol_cycle_snapshot_generation: generation 0 is compared with nothing, "
+                         "and snapshot_out must not be null");
+    *snapshot_out = golbatch::cycle_snapshot_generation(generation);
+    return GOL_OK;
+}
+
+int gol_cycle_step(gol_batch* batch, uint32_t generations, uint32_t* period_out, uint32_t* seen_out) {
+    if (!batch) return batch_err(nullptr, GOL_EINVAL, "gol_cycle_step: null handle");
+    if (generations == 0) return GOL_OK;
+    const size_t boards = (size_t)batch->geo.boards;
+    const uint32_t chunk = batch->chunk ? batch->chunk : golbatch::kAutoChunk;
+    BATCH_HIP(batch, hipSetDevice(batch->device));
+    if (!batch->cycle_words) {
+        const size_t bytes = (2 * boards + 2) * sizeof(uint32_t);
+        if (hipMalloc(&batch->cycle_words, bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            batch->cycle_words = nullptr;
+            return batch_err(batch, GOL_ENOMEM, "gol_cycle_step: hipMalloc of %zu bytes for the period and seen words "
+                             "failed; nothing advanced", bytes);
+        }
+    }
+    golbatch::CycleParams p{};
+    p.plane = batch->plane;
+    p.snap = batch->prev;
+    p.period = batch->cycle_words;
+    p.seen = batch->cycle_words + boards;
+    p.counters = batch->cycle_words + 2 * boards;
+    p.boards = batch->geo.boards;
+    p.width = batch->geo.width;
+    p.height = batch->geo.height;
+    p.boards_per_wave = batch->lanes.boards_per_wave;
+    p.vis_w = batch->geo.vis_w;
+    p.vis_h = batch->geo.vis_h;
+    p.birth = batch->birth;
+    p.survive = batch->survive;
+    // the first launch of a call reads neither the words nor the snapshot plane; the counters start at zero
+    BATCH_HIP(batch, hipMemsetAsync(p.counters, 0, 2 * sizeof(uint32_t), batch->stream));
+    batch->cycle_launches = 0;
+    uint32_t counters[2] = {0u, 0u};
+    for (uint32_t g0 = 0; g0 < generations; g0 += p.gens) {
+        // every board cycled: a launch fast-forwards, at most max_period - 1 generations per board whatever it is
+        // asked for, so the remainder goes as one launch unless a chunk launch is the shorter
+        const bool all = counters[0] == boards && counters[1] - 1u <= chunk;
+        p.gens = all ? generations - g0 : std::min(chunk, generations - g0);
+        p.g0 = g0;
+        BATCH_HIP(batch, golbatch::launch_batch_cycle(p, life_rule(batch), batch->geo.clipped, batch->stream));
+        batch->epoch += p.gens;
+        ++batch->cycle_launches;
+        BATCH_HIP(batch, hipMemcpyAsync(counters, p.counters, sizeof counters, hipMemcpyDeviceToHost, batch->stream));
+        BATCH_HIP(batch, hipStreamSynchronize(batch->stream));
+        batch->cycle_boards = counters[0];
+        batch->cycle_max_period = counters[1];
+    }
+    if (period_out)
+        BATCH_HIP(batch, hipMemcpyAsync(period_out, p.period, boards * sizeof(uint32_t), hipMemcpyDeviceToHost,
+                                        batch->stream));
+    if (seen_out)
+        BATCH_HIP(batch, hipMemcpyAsync(seen_out, p.seen, boards * sizeof(uint32_t), hipMemcpyDeviceToHost,
+                                        batch->stream));
+    BATCH_HIP(batch, hipStreamSynchronize(batch->stream));
+    return GOL_OK;
+}
+
+int gol_cycle_stats(gol_batch* batch, uint64_t* launches, uint64_t* boards_cycled, uint32_t* max_period) {
+    if (!batch) return batch_err(nullptr, GOL_EINVAL, "gol_cycle_stats: null handle");
+    if (launches) *launches = batch->cycle_launches;
+    if (boards_cycled) *boards_cycled = batch->cycle_boards;
+    if (max_period) *max_period = batch->cycle_max_period;
     return GOL_OK;
 }
 

@@ -80,10 +80,39 @@ struct StepParams {
     uint32_t birth, survive;
 };
 
+// Cycle detection's schedule (gol_cycle_step): Brent's
+// algorithm with snapshots at the generations t_k = 2^k - 1 of a call, a board
+// after g generations compared with the snapshot t_k < g <= t_{k+1}.  The one
+// place it is written: gol_cycle_snapshot_generation returns it, and the kernel
+// replaces the snapshot where cycle_is_snapshot says so and takes a board's
+// period from the generation its cycle was seen at.
+// The t_k that generation g >= 1 is compared with; right for every uint32_t g.
+__host__ __device__ inline uint32_t cycle_snapshot_generation(uint32_t g) {
+    return (1u << (31 - __builtin_clz(g))) - 1u;
+}
+// g is a t_k, k >= 1: the board after generation g becomes the snapshot
+// (2^32 - 1 is t_32: g + 1 wraps to 0).
+__host__ __device__ inline bool cycle_is_snapshot(uint32_t g) { return (g & (g + 1u)) == 0u; }
+
+// One launch of a cycle call: `gens` generations of every board, in place.
+struct CycleParams {
+    unsigned long long* plane;  // boards * height rows
+    unsigned long long* snap;   // the snapshot plane (the batch's `prev`); read when g0 > 0
+    uint32_t* period;           // [boards], 0 = no cycle seen yet; written with seen
+    uint32_t* seen;             // [boards], 0 = not yet; read when g0 > 0
+    uint32_t* counters;         // [0] boards that have a period, [1] the largest period
+    int32_t boards, width, height, boards_per_wave;
+    int32_t vis_w, vis_h;
+    uint32_t gens;              // generations of this launch
+    uint32_t g0;                // generations of the call before this launch
+    uint32_t birth, survive;
+};
+
 // life: the B3/S23 instances; clipped: the topology; null pops / settled: the
 // instance without that part.  hipErrorInvalidValue for parameters outside
 // what the kernels index safely.
 hipError_t launch_batch_step(const StepParams& p, bool life, bool clipped, hipStream_t stream);
+hipError_t launch_batch_cycle(const CycleParams& p, bool life, bool clipped, hipStream_t stream);
 hipError_t launch_batch_seed(unsigned long long* plane, int64_t words, int32_t width, uint64_t seed,
                              hipStream_t stream);
 // hashes[i] / pops[i] (either may be null) of boards first .. first + count - 1.

@@ -22,23 +22,19 @@
 //                         subtracts the prefix before its board and stores;
 //   settle (SETTLE)       the row against the row of two generations ago, a
 //                         ballot masked to the board's lanes.
+// The generation itself is gol_batch_gen.h's, shared with batch_cycle_kernel
+// (below: the same loops with cycle detection, early exit and fast-forward).
 // Idle lanes (past k * height, or of boards past the batch) compute along --
 // the loop has no lane branch around a cross-lane operation, so DPP and
 // permutes see every lane -- and contribute to nothing: active lanes never read them (torus) or read them as
 // dead rows (clipped), and they neither store, sum nor vote.
 #include "gol_batch.h"
+#include "gol_batch_gen.h"
 #include "gol_stencil.h"
 
 namespace golbatch {
 
-using namespace gol::dev;
-
 namespace {
-
-struct Row {
-    uint32_t lo, hi;
-};
-__device__ __forceinline__ Row row_of(uint32_t lo, uint32_t hi) { return Row{lo, hi}; }
 
 constexpr int kDppRowShr = 0x110;     // row_shr:n = kDppRowShr + n (rows of 16 lanes)
 constexpr int kDppRowBcast15 = 0x142;  // lane 15 of each row -> the next row
@@ -60,10 +56,6 @@ __device__ __forceinline__ uint32_t wave_prefix_sum(uint32_t v) {
     v = dpp_add<kDppRowBcast15, 0xa>(v);
     v = dpp_add<kDppRowBcast31, 0xc>(v);
     return v;
-}
-
-__device__ __forceinline__ uint32_t lane_read(int byte_addr, uint32_t v) {
-    return (uint32_t)__builtin_amdgcn_ds_bpermute(byte_addr, (int)v);
 }
 
 template <bool LIFE, bool CLIPPED, bool POP, bool SETTLE>
@@ -96,6 +88,7 @@ __global__ __launch_bounds__(kLanes* kWavesPerWG) void batch_step_kernel(const S
     // torus, height < 64: the lanes holding the rows above and below, inside the lane's own board
     const int up_addr = 4 * (active ? (y > 0 ? lane - 1 : lane + H - 1) : lane);
     const int dn_addr = 4 * (active ? (y < H - 1 ? lane + 1 : lane - (H - 1)) : lane);
+    const GenConsts C{wm_lo, wm_hi, wsh, sm_lo, sm_hi, upm, dnm, up_addr, dn_addr};
     // population: the board's last lane stores; the prefix before the board is the one of the lane before its
     // first (none before lane 0)
     const bool writer = active && y == H - 1;
@@ -123,78 +116,13 @@ __global__ __launch_bounds__(kLanes* kWavesPerWG) void batch_step_kernel(const S
         }
     }
 
-    // ROT: the wave is one torus board of 64 rows.  NARROW: width <= 32 -- a row's upper dword is zero and stays
-    // zero, so nothing is computed for it (the reference's 8 x 8 board: half the instructions).
+    // the four loops of gol_batch_gen.h's generation: rotates or permutes, wide or narrow
     auto run = [&](auto ROT_, auto NARROW_) __attribute__((always_inline)) {
         constexpr bool ROT = decltype(ROT_)::value;
         constexpr bool NARROW = decltype(NARROW_)::value;
         if constexpr (NARROW) cur.hi = prev.hi = 0u;
         for (uint32_t g = 0; g < p.gens; ++g) {
-            // rows above (a) and below (b); s: the centre as a neighbour sees it
-            Row a = {0u, 0u}, b = {0u, 0u}, s = cur;
-            if constexpr (CLIPPED) {
-                s = {cur.lo & sm_lo, NARROW ? 0u : cur.hi & sm_hi};
-                a.lo = dpp_shr1_zero(s.lo) & upm;
-                b.lo = dpp_shl1_zero(s.lo) & dnm;
-                if constexpr (!NARROW) {
-                    a.hi = dpp_shr1_zero(s.hi) & upm;
-                    b.hi = dpp_shl1_zero(s.hi) & dnm;
-                }
-            } else if constexpr (ROT) {
-                a.lo = dpp_ror1(cur.lo);
-                b.lo = dpp_rol1(cur.lo);
-                if constexpr (!NARROW) {
-                    a.hi = dpp_ror1(cur.hi);
-                    b.hi = dpp_rol1(cur.hi);
-                }
-            } else {
-                a.lo = lane_read(up_addr, cur.lo);
-                b.lo = lane_read(dn_addr, cur.lo);
-                if constexpr (!NARROW) {
-                    a.hi = lane_read(up_addr, cur.hi);
-                    b.hi = lane_read(dn_addr, cur.hi);
-                }
-            }
-            // column sums (v1 v0) = a + s + b, and their copies from the columns west and east
-            const Row v0 = row_of(GOL_BITOP3(a.lo, s.lo, b.lo, kXor3), NARROW ? 0u : GOL_BITOP3(a.hi, s.hi, b.hi, kXor3));
-            const Row v1 = row_of(GOL_BITOP3(a.lo, s.lo, b.lo, kMaj), NARROW ? 0u : GOL_BITOP3(a.hi, s.hi, b.hi, kMaj));
-            auto west = [&](const Row& v) -> Row {  // column x - 1 at bit x
-                Row w = row_of(v.lo << 1, NARROW ? 0u : __builtin_amdgcn_alignbit(v.hi, v.lo, 31));
-                if constexpr (!CLIPPED) w.lo |= ((NARROW ? v.lo : v.hi) >> wsh) & 1u;
-                return w;
-            };
-            auto east = [&](const Row& v) -> Row {  // column x + 1 at bit x
-                Row e = row_of(NARROW ? v.lo >> 1 : __builtin_amdgcn_alignbit(v.hi, v.lo, 1), v.hi >> 1);
-                if constexpr (!CLIPPED) {
-                    const uint32_t t = (v.lo & 1u) << wsh;
-                    if constexpr (NARROW) e.lo |= t;
-                    else e.hi |= t;
-                }
-                return e;
-            };
-            const Row w0 = west(v0), w1 = west(v1), e0 = east(v0), e1 = east(v1);
-            Row nx = {0u, 0u};
-            if constexpr (LIFE && !CLIPPED) {
-                nx.lo = rule_b3s23_fullsum(w0.lo, w1.lo, v0.lo, v1.lo, e0.lo, e1.lo, cur.lo);
-                if constexpr (!NARROW) nx.hi = rule_b3s23_fullsum(w0.hi, w1.hi, v0.hi, v1.hi, e0.hi, e1.hi, cur.hi);
-            } else {
-                auto half = [&](uint32_t aw, uint32_t bw, uint32_t ww0, uint32_t ww1, uint32_t ee0, uint32_t ee1,
-                                uint32_t al) -> uint32_t {
-                    const uint32_t p0 = aw ^ bw, p1 = aw & bw;  // the column minus its centre
-                    const uint32_t nb0 = GOL_BITOP3(ww0, ee0, p0, kXor3);
-                    const uint32_t c0 = GOL_BITOP3(ww0, ee0, p0, kMaj);
-                    const uint32_t pp = GOL_BITOP3(ww1, ee1, p1, kXor3);
-                    const uint32_t qq = GOL_BITOP3(ww1, ee1, p1, kMaj);
-                    uint32_t o;
-                    GOL_RULE_FROM_COUNT(o, LIFE, p, nb0, c0, pp, qq, al);
-                    return o;
-                };
-                nx.lo = half(a.lo, b.lo, w0.lo, w1.lo, e0.lo, e1.lo, cur.lo);
-                if constexpr (!NARROW) nx.hi = half(a.hi, b.hi, w0.hi, w1.hi, e0.hi, e1.hi, cur.hi);
-            }
-            nx.lo &= wm_lo;
-            if constexpr (!NARROW) nx.hi &= wm_hi;
-
+            const Row nx = generation<LIFE, CLIPPED, ROT, NARROW>(p, C, cur);
             if constexpr (POP) {
                 const uint32_t bits = (uint32_t)__builtin_popcount(nx.lo) + (NARROW ? 0u : (uint32_t)__builtin_popcount(nx.hi));
                 const uint32_t incl = wave_prefix_sum(active ? bits : 0u);
@@ -222,6 +150,103 @@ __global__ __launch_bounds__(kLanes* kWavesPerWG) void batch_step_kernel(const S
         if constexpr (SETTLE) {
             p.prev[idx] = (unsigned long long)prev.lo | ((unsigned long long)prev.hi << 32);
             if (y == 0) p.settled[board] = first;
+        }
+    }
+}
+
+// batch_cycle_kernel (gol_cycle_step): batch_step_kernel's
+// lane mapping and four loops, with Brent's cycle detection carried in
+// registers -- the snapshot row, and per lane a copy of the generation its
+// board's cycle was seen at (the period follows from it).  Per generation the new row against
+// the snapshot, a ballot masked to the board's lanes; the snapshot is replaced
+// at the generations 2^k - 1 of the call (scalar).  The main loop ends when
+// every board of the wave has a period (idle lanes count as done); then each
+// lane still owes (generations not run) mod period, and a second loop steps
+// the whole wave while any lane owes one, keeping the new row by a select
+// where the lane does.  Both loop conditions are ballots or scalars: no lane
+// branch surrounds a DPP or permute.  A wave with an undetected board keeps
+// stepping all its boards, which evolve truthfully.
+template <bool LIFE, bool CLIPPED>
+__global__ __launch_bounds__(kLanes* kWavesPerWG) void batch_cycle_kernel(const CycleParams p) {
+    const int lane = threadIdx.x & (kLanes - 1);
+    const int wave_in_wg = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / kLanes));
+    const int32_t wave = (int32_t)blockIdx.x * kWavesPerWG + wave_in_wg;  // waves <= boards <= 2^22
+    const int32_t board0 = wave * p.boards_per_wave;
+    if (board0 >= p.boards) return;  // the grid's last workgroup: wave-uniform, and nothing below synchronises
+    const Lane L = lane_of<CLIPPED>(p, lane, board0);
+    const GenConsts C = L.consts();
+    const unsigned long long bm = L.board_lanes();
+
+    // `seen` alone is carried through the loops: the period is seen - (the snapshot generation seen is compared with)
+    auto period_of = [](uint32_t seen_at) -> uint32_t {
+        return seen_at ? seen_at - cycle_snapshot_generation(seen_at) : 0u;
+    };
+    Row cur = {0u, 0u}, snap = {0u, 0u};
+    uint32_t seen = 1u;  // idle lanes: done with period 1, owing nothing
+    if (L.active) {
+        const unsigned long long r = p.plane[L.idx];
+        cur = {(uint32_t)r, (uint32_t)(r >> 32)};
+        seen = p.g0 > 0 ? p.seen[L.board] : 0u;
+    }
+    const uint32_t seen_in = seen;
+    // wave-uniform: some board of the wave has no period yet.  A later launch that finds none goes straight to the
+    // fast-forward and touches neither the snapshot plane nor the per-board words.
+    bool open = __builtin_amdgcn_ballot_w64(seen == 0u) != 0ull;
+    const bool ran = open;
+    if (ran) {
+        snap = cur;  // the call's generation 0 is t_0
+        if (L.active && p.g0 > 0) {
+            const unsigned long long q = p.snap[L.idx];
+            snap = {(uint32_t)q, (uint32_t)(q >> 32)};
+        }
+    }
+
+    auto run = [&](auto ROT_, auto NARROW_) __attribute__((always_inline)) {
+        constexpr bool ROT = decltype(ROT_)::value;
+        constexpr bool NARROW = decltype(NARROW_)::value;
+        if constexpr (NARROW) cur.hi = snap.hi = 0u;
+        uint32_t g = 0u;  // scalar: generations run
+        for (; g < p.gens && open; ++g) {
+            const Row nx = generation<LIFE, CLIPPED, ROT, NARROW>(p, C, cur);
+            const unsigned long long same =
+                __builtin_amdgcn_ballot_w64(nx.lo == snap.lo && (NARROW || nx.hi == snap.hi));
+            const uint32_t gen = p.g0 + g + 1u;  // generation of the call that nx is (<= 2^32 - 1)
+            seen = seen == 0u && (same & bm) == bm ? gen : seen;
+            if (cycle_is_snapshot(gen)) snap = nx;  // scalar
+            cur = nx;
+            open = __builtin_amdgcn_ballot_w64(seen == 0u) != 0ull;
+        }
+        // fast-forward: the loop above ended early only with a period in every lane; a board is on its cycle
+        const uint32_t period = period_of(seen);
+        uint32_t left = (p.gens - g) % (period ? period : 1u);
+        while (__builtin_amdgcn_ballot_w64(left > 0u) != 0ull) {
+            const Row nx = generation<LIFE, CLIPPED, ROT, NARROW>(p, C, cur);
+            const bool owes = left > 0u;
+            cur.lo = owes ? nx.lo : cur.lo;
+            if constexpr (!NARROW) cur.hi = owes ? nx.hi : cur.hi;
+            left -= owes ? 1u : 0u;
+        }
+    };
+    // wave-uniform, outside the loops
+    const bool rot = !CLIPPED && L.H == kLanes, narrow = p.width <= 32;
+    if (rot && narrow) run(std::true_type{}, std::true_type{});
+    else if (rot) run(std::true_type{}, std::false_type{});
+    else if (narrow) run(std::false_type{}, std::true_type{});
+    else run(std::false_type{}, std::false_type{});
+
+    if (L.active) {
+        p.plane[L.idx] = (unsigned long long)cur.lo | ((unsigned long long)cur.hi << 32);
+        if (ran) {
+            p.snap[L.idx] = (unsigned long long)snap.lo | ((unsigned long long)snap.hi << 32);
+            if (L.y == 0) {
+                const uint32_t period = period_of(seen);
+                p.period[L.board] = period;
+                p.seen[L.board] = seen;
+                if (seen_in == 0u && seen != 0u) {  // one lane per newly detected board
+                    atomicAdd(&p.counters[0], 1u);
+                    atomicMax(&p.counters[1], period);
+                }
+            }
         }
     }
 }
@@ -282,6 +307,23 @@ hipError_t launch_batch_step(const StepParams& p, bool life, bool clipped, hipSt
     const dim3 grid((unsigned)((waves + kWavesPerWG - 1) / kWavesPerWG));
     if (life) return clipped ? launch_step_flags<true, true>(p, grid, stream) : launch_step_flags<true, false>(p, grid, stream);
     return clipped ? launch_step_flags<false, true>(p, grid, stream) : launch_step_flags<false, false>(p, grid, stream);
+}
+
+hipError_t launch_batch_cycle(const CycleParams& p, bool life, bool clipped, hipStream_t stream) {
+    // every index the kernel forms stays inside the two planes and the per-board words
+    if (!p.plane || !p.snap || !p.period || !p.seen || !p.counters || p.boards < 1 || p.boards > kMaxBoards ||
+        p.width < 1 || p.width > kLanes || p.height < 1 || p.height > kLanes ||
+        p.boards_per_wave != batch_lanes(p.height, p.boards).boards_per_wave || p.gens < 1 ||
+        p.gens > UINT32_MAX - p.g0 ||
+        (clipped && (p.vis_w < 1 || p.vis_h < 1)))
+        return hipErrorInvalidValue;
+    const int64_t waves = batch_lanes(p.height, p.boards).waves;
+    const dim3 grid((unsigned)((waves + kWavesPerWG - 1) / kWavesPerWG)), block(kLanes * kWavesPerWG);
+    if (life)
+        return clipped ? gol::launch_kernel(batch_cycle_kernel<true, true>, grid, block, stream, p)
+                       : gol::launch_kernel(batch_cycle_kernel<true, false>, grid, block, stream, p);
+    return clipped ? gol::launch_kernel(batch_cycle_kernel<false, true>, grid, block, stream, p)
+                   : gol::launch_kernel(batch_cycle_kernel<false, false>, grid, block, stream, p);
 }
 
 hipError_t launch_batch_seed(unsigned long long* plane, int64_t words, int32_t width, uint64_t seed,

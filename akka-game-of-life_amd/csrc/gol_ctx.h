@@ -31,8 +31,9 @@
 //                      pattern search (gol_census, gol_read_region,
 //                      gol_write_region, gol_density, gol_find; the search
 //                      kernel is gol_find.hip)
-//   gol_batch.cpp      the batch engine (gol_batch_*): a handle type of its own
-//                      behind gol_batch.h, kernels in gol_batch.hip; it takes the
+//   gol_batch.cpp      the batch engine (gol_batch_*, gol_cycle_*): a handle type
+//                      of its own behind gol_batch.h, kernels in gol_batch.hip
+//                      (their shared generation: gol_batch_gen.h); it takes the
 //                      error state and the HIP status discipline from here
 //
 // Reference correspondence (src/main/scala/gameoflife/ of the reference):

@@ -226,6 +226,9 @@ _SIGNATURES = {
     "gol_batch_hashes": (_c.c_int, [_vp, _c.c_int64, _c.c_int64, _u64p, _u32p]),
     "gol_batch_epoch": (_c.c_int, [_vp, _u64p]),
     "gol_batch_set_chunk": (_c.c_int, [_vp, _c.c_uint32]),
+    "gol_cycle_step": (_c.c_int, [_vp, _c.c_uint32, _u32p, _u32p]),
+    "gol_cycle_snapshot_generation": (_c.c_int, [_c.c_uint32, _u32p]),
+    "gol_cycle_stats": (_c.c_int, [_vp, _u64p, _u64p, _u32p]),
 }
 
 

@@ -106,6 +106,25 @@ class GolBatch:
             return pop, st
         return pop if populations else st
 
+    def step_cycles(self, generations: int = 1) -> tuple[np.ndarray, np.ndarray]:
+        """Advance every board exactly as step(generations) does, with cycle
+        detection (gol_cycle_step): (period, seen), uint32 [boards] each -- the
+        board's exact minimal period and the generation of this call at which
+        its cycle was seen (Brent's schedule: snapshots at generations 2^k - 1),
+        0 and 0 where none was.  A board whose cycle has been seen costs at
+        most one period of stepping per launch."""
+        period = np.zeros(self.boards, dtype=np.uint32)
+        seen = np.zeros(self.boards, dtype=np.uint32)
+        self._chk(N.lib.gol_cycle_step(self._h, generations, period.ctypes.data_as(N._u32p),
+                                       seen.ctypes.data_as(N._u32p)))
+        return period, seen
+
+    def cycle_stats(self) -> dict:
+        """The last step_cycles call: launches, boards with a period, the largest period."""
+        launches, cycled, longest = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint32(0)
+        self._chk(N.lib.gol_cycle_stats(self._h, ctypes.byref(launches), ctypes.byref(cycled), ctypes.byref(longest)))
+        return {"launches": launches.value, "boards_cycled": cycled.value, "max_period": longest.value}
+
     def hashes(self) -> np.ndarray:
         """Each board's state hash (what GolEngine.hash() gives for the same cells)."""
         out = np.zeros(self.boards, dtype=np.uint64)

@@ -59,7 +59,9 @@ extern "C" {
  * and gol_find (the pattern search), and the batch engine with a handle type
  * of its own (gol_batch_geometry_get, gol_batch_create, gol_batch_destroy,
  * gol_batch_last_error, gol_batch_seed, gol_batch_load, gol_batch_snapshot,
- * gol_batch_step, gol_batch_hashes, gol_batch_epoch, gol_batch_set_chunk). */
+ * gol_batch_step, gol_batch_hashes, gol_batch_epoch, gol_batch_set_chunk), and
+ * its cycle detection (gol_cycle_step, gol_cycle_snapshot_generation,
+ * gol_cycle_stats). */
 #define GOL_ABI_VERSION 2
 
 /* Return codes. */
@@ -585,6 +587,51 @@ int gol_batch_epoch(const gol_batch* batch, uint64_t* epoch);
  * too -- so no single launch is long whatever a caller asks for.  0 = the
  * automatic value, 1024 (the chunk gol_step plans in). */
 int gol_batch_set_chunk(gol_batch* batch, uint32_t generations_per_launch);
+
+/* Cycle detection on a batch: gol_batch_step's
+ * settled_out only knows still lifes and period-2 ash, and a caller of
+ * gol_batch_step has to guess a generation count that every board then pays
+ * for.  gol_cycle_step advances every board `generations` generations and
+ * leaves exactly the boards and the epoch gol_batch_step(generations) leaves;
+ * per board it reports the exact minimal period of the cycle the board has
+ * entered and the generation of the call at which that was seen, and a board
+ * whose cycle has been seen costs no more than one period of stepping per
+ * launch, however many generations are asked for.  The names are not
+ * gol_batch_*: the handle is the batch, the capability its own.
+ *
+ * Detection is Brent's algorithm on a fixed schedule, the same for every board
+ * and, as settle detection, per call.  With x_g the board after g generations
+ * of the call, snapshots are taken at t_k = 2^k - 1 (0, 1, 3, 7, 15, ...), and
+ * for t_k < g <= t_{k+1} x_g is compared with x_{t_k}.  seen is the smallest
+ * such g with x_g == x_{t_k} and period = seen - t_k; both are 0 if there is
+ * none in this call.  The period is the minimal one: the first return to a
+ * state on the cycle comes after exactly one period, and a snapshot taken
+ * before the cycle is entered never recurs.  For a board that enters a cycle
+ * of period L after M generations, seen = t_k + L for the smallest k with
+ * t_k >= M and 2^k >= L: a block or a dead board (1, 1), a blinker (2, 3), a
+ * glider on a 64 x 64 torus (256, 511).
+ *
+ * period_out / seen_out (either nullable): [boards].  generations = 0 is
+ * GOL_OK and writes nothing.  Synchronises.  Launches go chunk by chunk under
+ * gol_batch_set_chunk (results never depend on it); after each the call reads
+ * two counters, and once every board has a period and the largest is at most
+ * chunk + 1 the remainder goes as one launch.  The snapshots live in the plane
+ * settle detection uses (a call is one or the other) and the per-board words
+ * are allocated by the first gol_cycle_step call (GOL_ENOMEM, nothing
+ * advanced, if they cannot be): gol_batch_geometry_get's device_bytes is what
+ * gol_batch_create allocates, as before.  GOL_EINVAL for a NULL handle. */
+int gol_cycle_step(gol_batch* batch, uint32_t generations, uint32_t* period_out, uint32_t* seen_out);
+
+/* The schedule: the snapshot generation t_k that `generation` >= 1 of a call
+ * is compared with (1 -> 0; 2, 3 -> 1; 4 .. 7 -> 3; 2^32 - 1 -> 2^31 - 1).
+ * Pure, needs no device.  GOL_EINVAL for generation 0 (compared with nothing)
+ * or a NULL snapshot_out. */
+int gol_cycle_snapshot_generation(uint32_t generation, uint32_t* snapshot_out);
+
+/* The last gol_cycle_step call of this batch: its launches, the boards that
+ * had a period when it returned and the largest of those periods (0 before
+ * the first call).  Any pointer may be NULL. */
+int gol_cycle_stats(gol_batch* batch, uint64_t* launches, uint64_t* boards_cycled, uint32_t* max_period);
 
 /* Kernel timing: when enabled, the dominant step-kernel launch of every pass
  * (the whole shard, or a sharded shard's interior rows) is bracketed by HIP
