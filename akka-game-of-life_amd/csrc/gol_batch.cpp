@@ -1,6 +1,7 @@
-// gol_batch.cpp -- C ABI of the batch engine (include/gol.h gol_batch_* and
-// gol_cycle_*; DESIGN.md sections 5f and 5g): many independent boards of at
-// most 64 x 64 stored cells stepped by one launch (kernels: gol_batch.hip).  A
+// gol_batch.cpp -- C ABI of the batch engine (include/gol.h gol_batch_*,
+// gol_cycle_* and gol_find_batch*; DESIGN.md sections 5f, 5g and 5h): many
+// independent boards of at most 64 x 64 stored cells stepped by one launch
+// (kernels: gol_batch.hip) and searched by one (gol_batch_find.hip).  A
 // handle type of its own: it shares the error conventions and the HIP status
 // discipline with the contexts (gol_ctx.h), and nothing else -- no planner, no
 // step kernel.
@@ -37,6 +38,16 @@ struct gol_batch {
     unsigned long long* hashes = nullptr;
     uint32_t* hash_pops = nullptr;
     size_t hashes_count = 0;
+    // gol_find_batch's buffers, grown on demand: the pattern table (headers, then the row pairs), the counts
+    // [boards][npatterns] and the match planes [npatterns][boards][height]
+    void* find_table = nullptr;
+    size_t find_table_bytes = 0;
+    uint32_t* find_counts = nullptr;
+    size_t find_counts_n = 0;
+    unsigned long long* find_matches = nullptr;
+    size_t find_matches_n = 0;
+    uint32_t find_cut = 0;  // gol_find_batch_set_cut (0: automatic)
+    uint64_t find_launches = 0, find_cared = 0;  // gol_find_batch_stats: the last gol_find_batch call
     std::string err;
 };
 
@@ -85,10 +96,35 @@ void destroy_impl(gol_batch* b) {
     hip_note(hipSetDevice(b->device), "batch destroy: hipSetDevice");
     if (b->stream) hip_note(hipStreamSynchronize(b->stream), "batch destroy: hipStreamSynchronize");
     for (void* p : {(void*)b->plane, (void*)b->prev, (void*)b->settled, (void*)b->series, (void*)b->hashes,
-                    (void*)b->hash_pops, (void*)b->cycle_words})
+                    (void*)b->hash_pops, (void*)b->cycle_words, b->find_table, (void*)b->find_counts,
+                    (void*)b->find_matches})
         if (p) hip_note(hipFree(p), "batch destroy: hipFree");
     if (b->stream) hip_note(hipStreamDestroy(b->stream), "batch destroy: hipStreamDestroy");
     delete b;
+}
+
+// A buffer of the handle that holds at least `want` elements of `elem` bytes (nothing is in flight on the old one:
+// every call synchronises).  False, with the buffer gone, if it cannot be had.
+template <class T>
+bool grow(T*& buf, size_t& have, size_t want, size_t elem) {
+    if (have >= want) return true;
+    if (buf) hip_note(hipFree(buf), "gol_find_batch: hipFree");
+    buf = nullptr;
+    have = 0;
+    void* p = nullptr;
+    if (hipMalloc(&p, want * elem) != hipSuccess) {
+        (void)hipGetLastError();
+        return false;
+    }
+    buf = static_cast<T*>(p);
+    have = want;
+    return true;
+}
+
+// "pattern 3: ..." or "...": batch_find_patterns' refusal as a message
+int find_refusal(gol_batch* b, const char* fn, const char* why, int32_t which) {
+    if (which >= 0) return batch_err(b, GOL_EINVAL, "%s: pattern %d: %s", fn, which, why);
+    return batch_err(b, GOL_EINVAL, "%s: %s", fn, why);
 }
 
 }  // namespace
@@ -364,6 +400,115 @@ int gol_batch_hashes(gol_batch* batch, int64_t first, int64_t count, uint64_t* h
         BATCH_HIP(batch, hipMemcpyAsync(populations_out, batch->hash_pops, n * sizeof(uint32_t), hipMemcpyDeviceToHost,
                                         batch->stream));
     BATCH_HIP(batch, hipStreamSynchronize(batch->stream));
+    return GOL_OK;
+}
+
+int gol_find_batch_check(const gol_batch_config* cfg, const gol_batch_pattern* patterns, int32_t npatterns) {
+    if (!cfg) return batch_err(nullptr, GOL_EINVAL, "gol_find_batch_check: null configuration");
+    golbatch::Geometry g;
+    if (const char* why = golbatch::batch_geometry(*cfg, &g))
+        return batch_err(nullptr, GOL_EINVAL, "batch of %d boards %d x %d: %s", cfg->boards, cfg->width, cfg->height,
+                         why);
+    int32_t which = -1;
+    if (const char* why = golbatch::batch_find_patterns(g, patterns, npatterns, &which))
+        return find_refusal(nullptr, "gol_find_batch_check", why, which);
+    return GOL_OK;
+}
+
+int gol_find_batch(gol_batch* batch, const gol_batch_pattern* patterns, int32_t npatterns, uint32_t* counts_out,
+                   size_t counts_capacity, uint64_t* matches_out, size_t matches_capacity) {
+    if (!batch) return batch_err(nullptr, GOL_EINVAL, "gol_find_batch: null handle");
+    int32_t which = -1;
+    if (const char* why = golbatch::batch_find_patterns(batch->geo, patterns, npatterns, &which))
+        return find_refusal(batch, "gol_find_batch", why, which);
+    if (!counts_out) return batch_err(batch, GOL_EINVAL, "gol_find_batch: counts_out is null");
+    const size_t boards = (size_t)batch->geo.boards, H = (size_t)batch->geo.height, np = (size_t)npatterns;
+    const size_t counts_n = boards * np, matches_n = np * boards * H;  // <= 2^8 * 2^22 * 2^6
+    if (counts_capacity < counts_n)
+        return batch_err(batch, GOL_EINVAL, "gol_find_batch: counts_out holds %zu entries, %zu boards x %d patterns "
+                         "need %zu", counts_capacity, boards, npatterns, counts_n);
+    if (matches_out && matches_capacity < matches_n)
+        return batch_err(batch, GOL_EINVAL, "gol_find_batch: matches_out holds %zu entries, %d patterns x %zu boards "
+                         "x %zu rows need %zu", matches_capacity, npatterns, boards, H, matches_n);
+
+    // the table: the headers, then per pattern row the pair (cells & care, care), bits at k >= pw cleared
+    size_t nrows = 0;
+    for (int32_t p = 0; p < npatterns; ++p) nrows += (size_t)patterns[p].ph;
+    const size_t head_bytes = np * sizeof(golbatch::FindPattern);  // a multiple of 16: the rows stay 8-byte aligned
+    const size_t table_bytes = head_bytes + nrows * 2 * sizeof(uint64_t);
+    std::vector<unsigned char> table(table_bytes);
+    auto* heads = reinterpret_cast<golbatch::FindPattern*>(table.data());
+    auto* rows = reinterpret_cast<uint64_t*>(table.data() + head_bytes);
+    uint32_t row0 = 0;
+    uint64_t cared_all = 0;
+    for (int32_t p = 0; p < npatterns; ++p) {
+        const gol_batch_pattern& q = patterns[p];
+        const uint64_t kmask = q.pw >= 64 ? ~0ull : (1ull << q.pw) - 1ull;
+        uint32_t cared = 0;
+        for (int32_t i = 0; i < q.ph; ++i) {
+            const uint64_t care = (q.care ? q.care[i] : ~0ull) & kmask;
+            rows[2 * ((size_t)row0 + (size_t)i)] = q.cells[i] & care;
+            rows[2 * ((size_t)row0 + (size_t)i) + 1] = care;
+            cared += (uint32_t)__builtin_popcountll(care);
+        }
+        heads[p] = {q.pw, q.ph, row0, cared};
+        row0 += (uint32_t)q.ph;
+        cared_all += cared;
+    }
+
+    BATCH_HIP(batch, hipSetDevice(batch->device));
+    if (!grow(batch->find_table, batch->find_table_bytes, table_bytes, 1) ||
+        !grow(batch->find_counts, batch->find_counts_n, counts_n, sizeof(uint32_t)) ||
+        (matches_out && !grow(batch->find_matches, batch->find_matches_n, matches_n, sizeof(unsigned long long))))
+        return batch_err(batch, GOL_ENOMEM, "gol_find_batch: hipMalloc of the pattern table (%zu bytes), the counts "
+                         "(%zu entries) or the match planes (%zu entries) failed; nothing written", table_bytes,
+                         counts_n, matches_out ? matches_n : (size_t)0);
+    // `table` outlives the copy: the call synchronises before it returns
+    BATCH_HIP(batch, hipMemcpyAsync(batch->find_table, table.data(), table_bytes, hipMemcpyHostToDevice, batch->stream));
+    golbatch::FindParams fp{};
+    fp.plane = batch->plane;
+    fp.counts = batch->find_counts;
+    fp.matches = matches_out ? batch->find_matches : nullptr;
+    fp.boards = batch->geo.boards;
+    fp.width = batch->geo.width;
+    fp.height = batch->geo.height;
+    fp.boards_per_wave = batch->lanes.boards_per_wave;
+    fp.npatterns = npatterns;
+    const auto* dev_heads = static_cast<const golbatch::FindPattern*>(batch->find_table);
+    const auto* dev_rows = reinterpret_cast<const unsigned long long*>(
+        static_cast<const unsigned char*>(batch->find_table) + head_bytes);
+    // the cut: as many patterns per launch as stay within the bound, one at least
+    const uint64_t cut = batch->find_cut ? batch->find_cut : golbatch::kAutoFindCut;
+    batch->find_launches = 0;
+    batch->find_cared = cared_all;
+    for (int32_t first = 0; first < npatterns; first += fp.count) {
+        uint64_t cared = heads[first].cared;
+        int32_t n = 1;
+        while (first + n < npatterns && cared + heads[first + n].cared <= cut) cared += heads[first + n++].cared;
+        fp.first = first;
+        fp.count = n;
+        BATCH_HIP(batch, golbatch::launch_batch_find(fp, dev_heads, dev_rows, batch->geo.clipped, batch->stream));
+        ++batch->find_launches;
+    }
+    BATCH_HIP(batch, hipMemcpyAsync(counts_out, batch->find_counts, counts_n * sizeof(uint32_t), hipMemcpyDeviceToHost,
+                                    batch->stream));
+    if (matches_out)
+        BATCH_HIP(batch, hipMemcpyAsync(matches_out, batch->find_matches, matches_n * sizeof(uint64_t),
+                                        hipMemcpyDeviceToHost, batch->stream));
+    BATCH_HIP(batch, hipStreamSynchronize(batch->stream));
+    return GOL_OK;
+}
+
+int gol_find_batch_set_cut(gol_batch* batch, uint32_t cared_cells_per_launch) {
+    if (!batch) return batch_err(nullptr, GOL_EINVAL, "gol_find_batch_set_cut: null handle");
+    batch->find_cut = cared_cells_per_launch;
+    return GOL_OK;
+}
+
+int gol_find_batch_stats(gol_batch* batch, uint64_t* launches, uint64_t* cared_cells) {
+    if (!batch) return batch_err(nullptr, GOL_EINVAL, "gol_find_batch_stats: null handle");
+    if (launches) *launches = batch->find_launches;
+    if (cared_cells) *cared_cells = batch->find_cared;
     return GOL_OK;
 }
 

@@ -66,6 +66,55 @@ inline uint64_t batch_device_bytes(const Geometry& g) {
     return 2 * plane + (uint64_t)g.boards * sizeof(uint32_t);
 }
 
+// Pattern search on a batch (gol_find_batch).
+constexpr int32_t kMaxFindPatterns = 256;
+// Cared cells per launch (gol_find_batch_set_cut 0): the pattern list is cut
+// into launches of at most this many, a pattern that has more alone in its
+// own.  Section 5h derives it from the measured cost per cared cell.
+constexpr uint32_t kAutoFindCut = 2048;
+
+// The patterns a batch of geometry g can be searched for, or the reason they
+// are refused (null: fine) and, in *which, the pattern it is about (-1: the
+// list).  What gol_find_batch_check reports and gol_find_batch does first.
+inline const char* batch_find_patterns(const Geometry& g, const gol_batch_pattern* patterns, int32_t npatterns,
+                                       int32_t* which) {
+    *which = -1;
+    if (!patterns) return "patterns is null";
+    if (npatterns < 1 || npatterns > kMaxFindPatterns) return "npatterns must be 1 .. 256";
+    for (int32_t p = 0; p < npatterns; ++p) {
+        const gol_batch_pattern& q = patterns[p];
+        *which = p;
+        if (q.pw < 1 || q.ph < 1 || q.pw > g.width || q.ph > g.height)
+            return "pw and ph must be 1 .. the boards' width and height";
+        if (!q.cells) return "cells is null";
+        if (q.care) {
+            const uint64_t kmask = q.pw >= 64 ? ~0ull : (1ull << q.pw) - 1ull;
+            uint64_t any = 0;
+            for (int32_t i = 0; i < q.ph; ++i) any |= q.care[i] & kmask;
+            if (!any) return "the pattern cares for no cell";
+        }
+    }
+    *which = -1;
+    return nullptr;
+}
+
+// The device's pattern table: per pattern its extents and the first of its ph
+// rows in the row array, a row being the qword pair (cells & care, care) with
+// the bits at k >= pw cleared.
+struct FindPattern {
+    int32_t pw, ph;
+    uint32_t row0, cared;  // cared: the pattern's cared cells (the launch cut counts them)
+};
+
+// One launch: patterns first .. first + count - 1 of the table against every board.
+struct FindParams {
+    const unsigned long long* plane;  // boards * height rows; read only
+    uint32_t* counts;                 // [boards][npatterns]
+    unsigned long long* matches;      // null, or [npatterns][boards][height]
+    int32_t boards, width, height, boards_per_wave;
+    int32_t npatterns, first, count;
+};
+
 // One launch: `gens` generations of every board, in place.
 struct StepParams {
     unsigned long long* plane;  // boards * height rows
@@ -118,5 +167,10 @@ hipError_t launch_batch_seed(unsigned long long* plane, int64_t words, int32_t w
 // hashes[i] / pops[i] (either may be null) of boards first .. first + count - 1.
 hipError_t launch_batch_hashes(const unsigned long long* plane, int32_t height, int64_t first, int64_t count,
                                unsigned long long* hashes, uint32_t* pops, hipStream_t stream);
+// gol_batch_find.hip.  hipErrorInvalidValue for parameters outside what the
+// kernel indexes safely; the table (`patterns`: [p.npatterns] headers, `rows`:
+// the row array they index) is the caller's to get right.
+hipError_t launch_batch_find(const FindParams& p, const FindPattern* patterns, const unsigned long long* rows,
+                             bool clipped, hipStream_t stream);
 
 }  // namespace golbatch

@@ -137,6 +137,19 @@ class GolBatchGeometry(ctypes.Structure):
     ]
 
 
+class GolBatchPattern(ctypes.Structure):
+    _fields_ = [
+        ("pw", ctypes.c_int32),
+        ("ph", ctypes.c_int32),
+        ("cells", ctypes.POINTER(ctypes.c_uint64)),
+        ("care", ctypes.POINTER(ctypes.c_uint64)),
+    ]
+
+
+# gol_find_batch: patterns per call, and the automatic launch cut in cared cells (include/gol.h)
+GOL_FIND_BATCH_MAX_PATTERNS = 256
+GOL_FIND_BATCH_AUTO_CUT = 2048
+
 # gol_write_region modes (include/gol.h GOL_REGION_*)
 GOL_REGION_COPY = 0
 GOL_REGION_OR = 1
@@ -229,6 +242,11 @@ _SIGNATURES = {
     "gol_cycle_step": (_c.c_int, [_vp, _c.c_uint32, _u32p, _u32p]),
     "gol_cycle_snapshot_generation": (_c.c_int, [_c.c_uint32, _u32p]),
     "gol_cycle_stats": (_c.c_int, [_vp, _u64p, _u64p, _u32p]),
+    "gol_find_batch_check": (_c.c_int, [ctypes.POINTER(GolBatchConfig), ctypes.POINTER(GolBatchPattern), _c.c_int32]),
+    "gol_find_batch": (_c.c_int, [_vp, ctypes.POINTER(GolBatchPattern), _c.c_int32, _u32p, _c.c_size_t, _u64p,
+                                  _c.c_size_t]),
+    "gol_find_batch_set_cut": (_c.c_int, [_vp, _c.c_uint32]),
+    "gol_find_batch_stats": (_c.c_int, [_vp, _u64p, _u64p]),
 }
 
 

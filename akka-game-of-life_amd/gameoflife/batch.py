@@ -14,6 +14,7 @@ import ctypes
 import numpy as np
 
 from . import _native as N
+from . import patterns as P
 from .rules import Rule, rule_by_name
 
 
@@ -137,6 +138,72 @@ class GolBatch:
         self._chk(N.lib.gol_batch_hashes(self._h, 0, self.boards, None, out.ctypes.data_as(N._u32p)))
         return out
 
+    def find(self, patterns, care=None, border: int = 0, orientations: bool = False, matches: bool = False):
+        """Count, and locate, patterns on every board, searched on the device
+        (gol_find_batch): uint32 [boards][P] -- entry [b][p] is the number of
+        anchors of board b at which pattern p matches.  `patterns` is one
+        pattern or a list of P; each, with `care` (one mask, or a list of P
+        with None where there is none) and `border`, is what patterns.as_search
+        takes (RLE text, O/. rows, a cell array; border=1: the object standing
+        alone).  An anchor is the board cell under the pattern's top-left
+        cell; the pattern wraps on a torus and reads dead beyond a clipped
+        board, as GolEngine.find.  matches=True: also uint64 [P][boards][H],
+        bit x of [p][b][y] set iff anchor (x, y) of board b matches pattern p
+        (match_positions lists them).  orientations=True: each pattern stands
+        for its distinct rotations and reflections (patterns.orientations):
+        its count is their sum and its match plane their OR, an anchor being
+        the top-left cell of the image that matched.  Changes nothing."""
+        one = isinstance(patterns, (str, P.Pattern)) or (
+            isinstance(patterns, (list, tuple)) and len(patterns) > 0 and all(isinstance(r, str) for r in patterns)) or (
+            isinstance(patterns, np.ndarray) and patterns.ndim == 2)
+        plist = [patterns] if one else list(patterns)
+        cares = [care] * len(plist) if one or care is None else list(care)
+        if not plist or len(cares) != len(plist):
+            raise ValueError("find takes at least one pattern, and one care mask per pattern if any")
+        images, owner = [], []  # the patterns the device searches for, and the asked pattern each stands for
+        for i, (pat, msk) in enumerate(zip(plist, cares)):
+            cells, mask = P.as_search(pat, msk, border)
+            for img in (P.orientations(cells, mask) if orientations else [(cells, mask)]):
+                if img[0].shape[1] > self.width or img[0].shape[0] > self.height:
+                    if orientations and img[0].shape != cells.shape:
+                        continue  # a turned image that does not fit the board matches nowhere
+                    raise ValueError(f"pattern {i} ({img[0].shape[1]} x {img[0].shape[0]}, border included) does not "
+                                     f"fit a {self.width} x {self.height} board")
+                images.append(img)
+                owner.append(i)
+        n = len(images)
+        if n > N.GOL_FIND_BATCH_MAX_PATTERNS:
+            raise ValueError(f"{n} patterns (orientations included) in one call; at most "
+                             f"{N.GOL_FIND_BATCH_MAX_PATTERNS}")
+        rows = [(pack_rows(c[None])[0], pack_rows(m[None])[0]) for c, m in images]  # kept alive through the call
+        table = (N.GolBatchPattern * n)()
+        for t, (c, _), (rc, rm) in zip(table, images, rows):
+            t.ph, t.pw = c.shape
+            t.cells, t.care = rc.ctypes.data_as(N._u64p), rm.ctypes.data_as(N._u64p)
+        counts = np.zeros((self.boards, n), dtype=np.uint32)
+        planes = np.zeros((n, self.boards, self.height), dtype=np.uint64) if matches else None
+        self._chk(N.lib.gol_find_batch(self._h, table, n, counts.ctypes.data_as(N._u32p), counts.size,
+                                       planes.ctypes.data_as(N._u64p) if matches else None,
+                                       planes.size if matches else 0))
+        if orientations:  # fold the images back into the patterns asked for
+            own = np.asarray(owner)
+            counts = np.stack([counts[:, own == i].sum(axis=1, dtype=np.uint32) for i in range(len(plist))], axis=1)
+            if matches:
+                planes = np.stack([np.bitwise_or.reduce(planes[own == i], axis=0) if (own == i).any()
+                                   else np.zeros((self.boards, self.height), dtype=np.uint64)
+                                   for i in range(len(plist))])
+        return (counts, planes) if matches else counts
+
+    def set_find_cut(self, cared_cells: int) -> None:
+        """Knob: cared cells per launch of find (0: automatic); results never depend on it."""
+        self._chk(N.lib.gol_find_batch_set_cut(self._h, cared_cells))
+
+    def find_stats(self) -> dict:
+        """The last find call: its launches and the cared cells of its patterns."""
+        launches, cared = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        self._chk(N.lib.gol_find_batch_stats(self._h, ctypes.byref(launches), ctypes.byref(cared)))
+        return {"launches": launches.value, "cared_cells": cared.value}
+
     @property
     def epoch(self) -> int:
         e = ctypes.c_uint64(0)
@@ -155,6 +222,14 @@ def pack_rows(cells) -> np.ndarray:
         raise ValueError(f"cells must be [n][H][W] with W <= 64, not {c.shape}")
     weights = np.uint64(1) << np.arange(c.shape[2], dtype=np.uint64)
     return ((c != 0).astype(np.uint64) * weights).sum(axis=2, dtype=np.uint64)
+
+
+def match_positions(rows, width: int) -> np.ndarray:
+    """One pattern's match plane (GolBatch.find(..., matches=True)[1][p]: uint64
+    [boards][H]) as int64 [n][3] of (board, x, y), sorted by (board, y, x)."""
+    bits = unpack_rows(rows, width)
+    b, y, x = np.nonzero(bits)  # row-major: sorted by (board, y, x)
+    return np.stack([b, x, y], axis=1).astype(np.int64)
 
 
 def unpack_rows(rows, width: int) -> np.ndarray:

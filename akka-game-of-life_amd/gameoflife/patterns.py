@@ -195,6 +195,31 @@ def as_search(pattern, care=None, border: int = 0) -> tuple[np.ndarray, np.ndarr
     return np.ascontiguousarray(cells & asked, dtype=np.uint8), np.ascontiguousarray(asked, dtype=np.uint8)
 
 
+def orientations(cells, care=None) -> list[tuple[np.ndarray, np.ndarray]]:
+    """The distinct images of a search pattern under the 8 symmetries of the
+    square (4 rotations, each also mirrored), as (cells, care) pairs of uint8
+    arrays in the order they are first met, the pattern itself first.  `care`
+    (default: every cell) turns with the cells; two images are the same when
+    their shapes, care masks and cared cells are equal.  A block has 1, a
+    blinker 2, a glider 8.  Turning commutes with as_search's border."""
+    c = np.asarray(cells, dtype=np.uint8) & 1
+    m = np.ones_like(c) if care is None else (np.asarray(care) != 0).astype(np.uint8)
+    if c.ndim != 2 or c.shape[0] < 1 or c.shape[1] < 1 or m.shape != c.shape:
+        raise ValueError("orientations takes a non-empty [h][w] cell array and a care mask of its shape")
+    c = c & m
+    out, seen = [], set()
+    for flip in (False, True):
+        fc, fm = (c[:, ::-1], m[:, ::-1]) if flip else (c, m)
+        for turns in range(4):
+            ic = np.ascontiguousarray(np.rot90(fc, turns))
+            im = np.ascontiguousarray(np.rot90(fm, turns))
+            key = (ic.shape, ic.tobytes(), im.tobytes())
+            if key not in seen:
+                seen.add(key)
+                out.append((ic, im))
+    return out
+
+
 def match_band(band, cells, care) -> np.ndarray:
     """Host matcher for the few anchors a device search leaves to its caller
     (ShardGroup.find): bool [bh - ph + 1][bw - pw + 1], entry (j, i) true iff

@@ -61,7 +61,8 @@ extern "C" {
  * gol_batch_last_error, gol_batch_seed, gol_batch_load, gol_batch_snapshot,
  * gol_batch_step, gol_batch_hashes, gol_batch_epoch, gol_batch_set_chunk), and
  * its cycle detection (gol_cycle_step, gol_cycle_snapshot_generation,
- * gol_cycle_stats). */
+ * gol_cycle_stats) and its pattern search (gol_find_batch_check,
+ * gol_find_batch, gol_find_batch_set_cut, gol_find_batch_stats). */
 #define GOL_ABI_VERSION 2
 
 /* Return codes. */
@@ -632,6 +633,67 @@ int gol_cycle_snapshot_generation(uint32_t generation, uint32_t* snapshot_out);
  * had a period when it returned and the largest of those periods (0 before
  * the first call).  Any pointer may be NULL. */
 int gol_cycle_stats(gol_batch* batch, uint64_t* launches, uint64_t* boards_cycled, uint32_t* max_period);
+
+/* Pattern search on a batch: what the ash of a soup
+ * run is -- how many blocks, blinkers, beehives and gliders each board holds,
+ * which boards hold a given object, and where -- answered on the device for
+ * every board at once: a list of patterns is matched against every board in
+ * one launch, and only a [boards][patterns] table of counts and, if asked for,
+ * the match bits cross the bus.  gol_find above works on contexts; a context
+ * per board costs more than the search.  As with gol_cycle_* the names are not
+ * gol_batch_*: the handle is the batch, the capability its own.
+ *
+ * A pattern is ph rows in the batch's host row layout: bit k of cells[i] is
+ * pattern cell (k, i); a care bit of 1: the board cell must equal the pattern
+ * bit, 0: don't care; care = NULL cares for every cell of the pw x ph box.
+ * Bits at k >= pw are ignored in both.  1 <= pw <= width, 1 <= ph <= height,
+ * at least one cared cell; a pattern with no live cared cell (an empty 3 x 3
+ * box) is legal.
+ *
+ * The semantics are gol_find's ("Pattern search" above) with the window of
+ * anchors the whole stored board: anchor (x, y) of board b matches pattern p
+ * iff for every cared cell (k, i) board cell (x + k, y + i) equals pattern
+ * cell (k, i); the coordinates wrap modulo width and height on GOL_TORUS; on
+ * GOL_REF_CLIPPED cells beyond the stored board read dead, and the stored
+ * cells outside the visible extent are cells like any other.  A context
+ * holding a board's cells gives the same answer from gol_find.
+ *
+ * counts_out (required): [boards][npatterns] -- entry [b * npatterns + p] is
+ * the exact number of matching anchors.  matches_out (nullable):
+ * [npatterns][boards][height] -- bit x of entry [(p * boards + b) * height + y]
+ * is set iff anchor (x, y) matches; bits at x >= width are zero.  The
+ * capacities are sizes in entries.
+ *
+ * gol_find_batch synchronises and changes neither the boards, the epoch, the
+ * hashes nor anything a later gol_batch_step or gol_cycle_step reads (both
+ * are per call; the plane settle and cycle detection keep is not written).
+ * The device buffers (pattern table, counts, match planes) belong to the
+ * handle and grow on demand (GOL_ENOMEM, and nothing written, if they cannot);
+ * gol_batch_geometry_get's device_bytes is what gol_batch_create allocates, as
+ * before.  NULL arguments, npatterns outside 1 .. 256, sizes out of range, a
+ * NULL cells, a pattern with no cared cell and a short capacity return
+ * GOL_EINVAL with a message before any device work and leave both outputs
+ * untouched.  gol_find_batch_check validates a pattern list for a geometry as
+ * gol_find_batch does and needs no device (as gol_batch_geometry_get). */
+typedef struct gol_batch_pattern {
+    int32_t pw, ph;            /* 1 <= pw <= width, 1 <= ph <= height of the batch's boards */
+    const uint64_t* cells;     /* ph rows, bit k = pattern column k */
+    const uint64_t* care;      /* ph rows, or NULL: care for all pw x ph */
+} gol_batch_pattern;
+int gol_find_batch_check(const gol_batch_config* cfg, const gol_batch_pattern* patterns, int32_t npatterns);
+int gol_find_batch(gol_batch* batch, const gol_batch_pattern* patterns, int32_t npatterns,
+                   uint32_t* counts_out, size_t counts_capacity,
+                   uint64_t* matches_out, size_t matches_capacity);
+
+/* Knob (results never depend on it): the pattern list is cut into launches of
+ * at most this many cared cells (a pattern that has more goes alone), so no
+ * single launch is long whatever a caller asks for.  0 = the automatic value,
+ * 2048 (DESIGN.md section 5h derives it). */
+int gol_find_batch_set_cut(gol_batch* batch, uint32_t cared_cells_per_launch);
+
+/* The last gol_find_batch call of this batch: its launches and the cared cells
+ * of its patterns (0 before the first call).  Either pointer may be NULL. */
+int gol_find_batch_stats(gol_batch* batch, uint64_t* launches, uint64_t* cared_cells);
 
 /* Kernel timing: when enabled, the dominant step-kernel launch of every pass
  * (the whole shard, or a sharded shard's interior rows) is bracketed by HIP
