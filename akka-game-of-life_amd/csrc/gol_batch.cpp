@@ -1,7 +1,8 @@
 // gol_batch.cpp -- C ABI of the batch engine (include/gol.h gol_batch_*,
-// gol_cycle_* and gol_find_batch*; DESIGN.md sections 5f, 5g and 5h): many
-// independent boards of at most 64 x 64 stored cells stepped by one launch
-// (kernels: gol_batch.hip) and searched by one (gol_batch_find.hip).  A
+// gol_cycle_*, gol_find_batch* and gol_objects_batch*; DESIGN.md sections 5f
+// to 5i): many independent boards of at most 64 x 64 stored cells stepped by
+// one launch (kernels: gol_batch.hip), searched by one (gol_batch_find.hip)
+// and cut into their objects by one (gol_batch_objects.hip).  A
 // handle type of its own: it shares the error conventions and the HIP status
 // discipline with the contexts (gol_ctx.h), and nothing else -- no planner, no
 // step kernel.
@@ -48,6 +49,13 @@ struct gol_batch {
     size_t find_matches_n = 0;
     uint32_t find_cut = 0;  // gol_find_batch_set_cut (0: automatic)
     uint64_t find_launches = 0, find_cared = 0;  // gol_find_batch_stats: the last gol_find_batch call
+    // gol_objects_batch's buffers, grown on demand: the counts [count] and the records [count][max_objects]
+    uint32_t* obj_counts = nullptr;
+    size_t obj_counts_n = 0;
+    gol_batch_object* obj_records = nullptr;
+    size_t obj_records_n = 0;
+    // gol_objects_batch_stats: the last gol_objects_batch call
+    uint64_t obj_launches = 0, obj_total = 0, obj_truncated = 0;
     std::string err;
 };
 
@@ -97,7 +105,7 @@ void destroy_impl(gol_batch* b) {
     if (b->stream) hip_note(hipStreamSynchronize(b->stream), "batch destroy: hipStreamSynchronize");
     for (void* p : {(void*)b->plane, (void*)b->prev, (void*)b->settled, (void*)b->series, (void*)b->hashes,
                     (void*)b->hash_pops, (void*)b->cycle_words, b->find_table, (void*)b->find_counts,
-                    (void*)b->find_matches})
+                    (void*)b->find_matches, (void*)b->obj_counts, (void*)b->obj_records})
         if (p) hip_note(hipFree(p), "batch destroy: hipFree");
     if (b->stream) hip_note(hipStreamDestroy(b->stream), "batch destroy: hipStreamDestroy");
     delete b;
@@ -509,6 +517,82 @@ int gol_find_batch_stats(gol_batch* batch, uint64_t* launches, uint64_t* cared_c
     if (!batch) return batch_err(nullptr, GOL_EINVAL, "gol_find_batch_stats: null handle");
     if (launches) *launches = batch->find_launches;
     if (cared_cells) *cared_cells = batch->find_cared;
+    return GOL_OK;
+}
+
+int gol_objects_batch_check(const gol_batch_config* cfg, int64_t first, int64_t count, int32_t reach,
+                            int32_t max_objects) {
+    if (!cfg) return batch_err(nullptr, GOL_EINVAL, "gol_objects_batch_check: null configuration");
+    golbatch::Geometry g;
+    if (const char* why = golbatch::batch_geometry(*cfg, &g))
+        return batch_err(nullptr, GOL_EINVAL, "batch of %d boards %d x %d: %s", cfg->boards, cfg->width, cfg->height,
+                         why);
+    if (const char* why = golbatch::batch_objects_args(g, first, count, reach, max_objects))
+        return batch_err(nullptr, GOL_EINVAL, "gol_objects_batch_check: %s (first %lld, count %lld, reach %d, "
+                         "max_objects %d, batch of %d)", why, (long long)first, (long long)count, reach, max_objects,
+                         g.boards);
+    return GOL_OK;
+}
+
+int gol_objects_batch(gol_batch* batch, int64_t first, int64_t count, int32_t reach, int32_t max_objects,
+                      uint32_t* counts_out, size_t counts_capacity, gol_batch_object* objects_out,
+                      size_t objects_capacity) {
+    static_assert(sizeof(gol_batch_object) == sizeof(uint4), "a record is one 16-byte store");
+    if (!batch) return batch_err(nullptr, GOL_EINVAL, "gol_objects_batch: null handle");
+    if (const char* why = golbatch::batch_objects_args(batch->geo, first, count, reach, max_objects))
+        return batch_err(batch, GOL_EINVAL, "gol_objects_batch: %s (first %lld, count %lld, reach %d, max_objects %d, "
+                         "batch of %d)", why, (long long)first, (long long)count, reach, max_objects,
+                         batch->geo.boards);
+    if (!counts_out || !objects_out)
+        return batch_err(batch, GOL_EINVAL, "gol_objects_batch: counts_out or objects_out is null");
+    const size_t n = (size_t)count, records_n = n * (size_t)max_objects;  // <= 2^22 * 2^10
+    if (counts_capacity < n)
+        return batch_err(batch, GOL_EINVAL, "gol_objects_batch: counts_out holds %zu entries, %zu boards need %zu",
+                         counts_capacity, n, n);
+    if (objects_capacity < records_n)
+        return batch_err(batch, GOL_EINVAL, "gol_objects_batch: objects_out holds %zu entries, %zu boards x %d "
+                         "objects need %zu", objects_capacity, n, max_objects, records_n);
+
+    BATCH_HIP(batch, hipSetDevice(batch->device));
+    if (!grow(batch->obj_counts, batch->obj_counts_n, n, sizeof(uint32_t)) ||
+        !grow(batch->obj_records, batch->obj_records_n, records_n, sizeof(gol_batch_object)))
+        return batch_err(batch, GOL_ENOMEM, "gol_objects_batch: hipMalloc of the counts (%zu entries) or the records "
+                         "(%zu entries) failed; nothing written", n, records_n);
+    // the records past a board's count are zero: one memset before the launch, the kernel stores the real ones only
+    BATCH_HIP(batch, hipMemsetAsync(batch->obj_records, 0, records_n * sizeof(gol_batch_object), batch->stream));
+    golbatch::ObjectsParams p{};
+    p.plane = batch->plane;
+    p.counts = batch->obj_counts;
+    p.objects = reinterpret_cast<uint4*>(batch->obj_records);
+    p.boards = (int32_t)(first + count);
+    p.width = batch->geo.width;
+    p.height = batch->geo.height;
+    p.boards_per_wave = batch->lanes.boards_per_wave;
+    p.vis_w = batch->geo.vis_w;
+    p.vis_h = batch->geo.vis_h;
+    p.first = (int32_t)first;
+    p.reach = reach;
+    p.max_objects = max_objects;
+    BATCH_HIP(batch, golbatch::launch_batch_objects(p, batch->geo.clipped, batch->stream));
+    BATCH_HIP(batch, hipMemcpyAsync(counts_out, batch->obj_counts, n * sizeof(uint32_t), hipMemcpyDeviceToHost,
+                                    batch->stream));
+    BATCH_HIP(batch, hipMemcpyAsync(objects_out, batch->obj_records, records_n * sizeof(gol_batch_object),
+                                    hipMemcpyDeviceToHost, batch->stream));
+    BATCH_HIP(batch, hipStreamSynchronize(batch->stream));
+    batch->obj_launches = 1;
+    batch->obj_total = batch->obj_truncated = 0;
+    for (size_t i = 0; i < n; ++i) {
+        batch->obj_total += counts_out[i];
+        batch->obj_truncated += counts_out[i] > (uint32_t)max_objects ? 1u : 0u;
+    }
+    return GOL_OK;
+}
+
+int gol_objects_batch_stats(gol_batch* batch, uint64_t* launches, uint64_t* objects, uint64_t* boards_truncated) {
+    if (!batch) return batch_err(nullptr, GOL_EINVAL, "gol_objects_batch_stats: null handle");
+    if (launches) *launches = batch->obj_launches;
+    if (objects) *objects = batch->obj_total;
+    if (boards_truncated) *boards_truncated = batch->obj_truncated;
     return GOL_OK;
 }
 

@@ -173,4 +173,36 @@ hipError_t launch_batch_hashes(const unsigned long long* plane, int32_t height, 
 hipError_t launch_batch_find(const FindParams& p, const FindPattern* patterns, const unsigned long long* rows,
                              bool clipped, hipStream_t stream);
 
+// The objects of a batch's boards (gol_objects_batch).
+// Two live cells of one 2 x 2 tile are always linked, so a board of at most
+// 64 x 64 cells has at most 32 * 32 objects.
+constexpr int32_t kMaxBoardObjects = 1024;
+
+// The boards, reach and records per board that a batch of geometry g can be
+// asked for, or the reason they are refused (null: fine).  What
+// gol_objects_batch_check reports and gol_objects_batch does first.
+inline const char* batch_objects_args(const Geometry& g, int64_t first, int64_t count, int32_t reach,
+                                      int32_t max_objects) {
+    if (reach != 1 && reach != 2) return "reach must be 1 or 2";
+    if (max_objects < 1 || max_objects > kMaxBoardObjects) return "max_objects must be 1 .. 1024";
+    if (first < 0 || count < 1 || first >= g.boards || count > (int64_t)g.boards - first)
+        return "boards [first, first + count) outside the batch";
+    return nullptr;
+}
+
+// One launch: the objects of boards first .. boards - 1.
+struct ObjectsParams {
+    const unsigned long long* plane;  // the batch's rows; read only
+    uint32_t* counts;                 // [boards - first]
+    uint4* objects;                   // [boards - first][max_objects] gol_batch_object records, zeroed by the caller
+    int32_t boards;                   // the end of the range, <= the batch's boards
+    int32_t width, height, boards_per_wave;
+    int32_t vis_w, vis_h;
+    int32_t first, reach, max_objects;
+};
+
+// gol_batch_objects.hip.  hipErrorInvalidValue for parameters outside what
+// the kernel indexes safely.
+hipError_t launch_batch_objects(const ObjectsParams& p, bool clipped, hipStream_t stream);
+
 }  // namespace golbatch

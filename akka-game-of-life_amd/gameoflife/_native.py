@@ -146,6 +146,22 @@ class GolBatchPattern(ctypes.Structure):
     ]
 
 
+class GolBatchObject(ctypes.Structure):
+    """gol_batch_object: one object of a board (gol_objects_batch)."""
+    _fields_ = [
+        ("hash", ctypes.c_uint64),
+        ("x", ctypes.c_uint8),
+        ("y", ctypes.c_uint8),
+        ("w", ctypes.c_uint8),
+        ("h", ctypes.c_uint8),
+        ("population", ctypes.c_uint16),
+        ("reserved", ctypes.c_uint16),
+    ]
+
+
+# gol_objects_batch: the most objects a board can have (include/gol.h)
+GOL_OBJECTS_BATCH_MAX = 1024
+
 # gol_find_batch: patterns per call, and the automatic launch cut in cared cells (include/gol.h)
 GOL_FIND_BATCH_MAX_PATTERNS = 256
 GOL_FIND_BATCH_AUTO_CUT = 2048
@@ -247,6 +263,11 @@ _SIGNATURES = {
                                   _c.c_size_t]),
     "gol_find_batch_set_cut": (_c.c_int, [_vp, _c.c_uint32]),
     "gol_find_batch_stats": (_c.c_int, [_vp, _u64p, _u64p]),
+    "gol_objects_batch_check": (_c.c_int, [ctypes.POINTER(GolBatchConfig), _c.c_int64, _c.c_int64, _c.c_int32,
+                                           _c.c_int32]),
+    "gol_objects_batch": (_c.c_int, [_vp, _c.c_int64, _c.c_int64, _c.c_int32, _c.c_int32, _u32p, _c.c_size_t,
+                                     ctypes.POINTER(GolBatchObject), _c.c_size_t]),
+    "gol_objects_batch_stats": (_c.c_int, [_vp, _u64p, _u64p, _u64p]),
 }
 
 

@@ -17,6 +17,9 @@ from . import _native as N
 from . import patterns as P
 from .rules import Rule, rule_by_name
 
+# gol_batch_object as a numpy record (N.GolBatchObject's fields in its order, 16 bytes)
+OBJECT_DTYPE = P.OBJECT_DTYPE
+
 
 class GolBatch:
     """A batch of boards on one GPU (gol_batch_create .. gol_batch_destroy)."""
@@ -204,6 +207,34 @@ class GolBatch:
         self._chk(N.lib.gol_find_batch_stats(self._h, ctypes.byref(launches), ctypes.byref(cared)))
         return {"launches": launches.value, "cared_cells": cared.value}
 
+    def objects(self, reach: int = 1, max_objects: int = 64, first: int = 0, count: int | None = None):
+        """Every board cut into its objects on the device (gol_objects_batch):
+        (counts uint32 [n], objects OBJECT_DTYPE [n][max_objects]) for boards
+        first .. first + n - 1.  Two live cells belong to one object iff a
+        chain of live cells joins them whose steps have Chebyshev distance at
+        most `reach` (1: 8-connectivity; 2: islands that can influence a
+        common cell), cyclic on a torus; what find(..., border=reach) reports
+        is such an object.  counts[b] is exact; objects[b][j] holds object j
+        for j < min(counts[b], max_objects) in the order of the objects' first
+        cells (row-major), zeros beyond: a translation-invariant hash
+        (patterns.object_hash of the object's cells), the bounding box x, y,
+        w, h (w == width on a torus: the object goes round) and the
+        population.  Changes nothing."""
+        count = self.boards - first if count is None else count
+        counts = np.zeros(max(count, 0), dtype=np.uint32)
+        objs = np.zeros((max(count, 0), max(max_objects, 0)), dtype=OBJECT_DTYPE)
+        self._chk(N.lib.gol_objects_batch(self._h, first, count, reach, max_objects, counts.ctypes.data_as(N._u32p),
+                                          counts.size, objs.ctypes.data_as(ctypes.POINTER(N.GolBatchObject)),
+                                          objs.size))
+        return counts, objs
+
+    def objects_stats(self) -> dict:
+        """The last objects call: its launches, its objects in all, the boards with more than max_objects."""
+        launches, total, cut = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint64(0)
+        self._chk(N.lib.gol_objects_batch_stats(self._h, ctypes.byref(launches), ctypes.byref(total),
+                                                ctypes.byref(cut)))
+        return {"launches": launches.value, "objects": total.value, "boards_truncated": cut.value}
+
     @property
     def epoch(self) -> int:
         e = ctypes.c_uint64(0)
@@ -213,6 +244,25 @@ class GolBatch:
     def set_chunk(self, n: int) -> None:
         """Generations per launch (0: automatic); results never depend on it."""
         self._chk(N.lib.gol_batch_set_chunk(self._h, n))
+
+
+def tally(counts, objects, table) -> dict:
+    """A census of what GolBatch.objects returned: name -> number of objects,
+    over all boards, by `table` (patterns.object_table: (hash, w, h,
+    population) -> name); the objects the table does not name are counted
+    under None.  Only the records present count (min(count, max_objects) per
+    board)."""
+    counts = np.asarray(counts)
+    objects = np.asarray(objects)
+    kept = np.arange(objects.shape[1])[None, :] < counts[:, None]
+    recs = objects[kept]
+    cols = np.stack([recs[f].astype(np.uint64) for f in ("hash", "w", "h", "population")], axis=1)
+    keys, n = np.unique(cols, axis=0, return_counts=True)
+    out: dict = {}
+    for k, c in zip(keys.tolist(), n.tolist()):
+        name = table.get(tuple(k))
+        out[name] = out.get(name, 0) + c
+    return out
 
 
 def pack_rows(cells) -> np.ndarray:

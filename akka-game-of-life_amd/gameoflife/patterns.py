@@ -235,3 +235,146 @@ def match_band(band, cells, care) -> np.ndarray:
     for i, k in zip(*np.nonzero(care)):
         ok &= band[i:i + nh, k:k + nw] == cells[i, k]
     return ok
+
+
+# ---------------------------------------------------------------- objects
+# gol_batch_object (include/gol.h) as a numpy record: what GolBatch.objects
+# returns and label_objects computes on the host
+OBJECT_DTYPE = np.dtype([("hash", "<u8"), ("x", "u1"), ("y", "u1"), ("w", "u1"), ("h", "u1"),
+                         ("population", "<u2"), ("reserved", "<u2")])
+
+_M32 = np.uint64(0xFFFFFFFF)
+
+
+def _hash_cells(c: np.ndarray) -> int:
+    """The state hash (DESIGN.md section 5, row0 = 0) of a uint8 [h][w] cell
+    array as it stands: per row y and column group g (columns 64 g ..
+    64 g + 63) the words E (even columns) and O (odd columns) contribute
+    (E A(y, 0) + O A(y, 1)) B(g) modulo 2^64."""
+    h, w = c.shape
+    groups = (w + 63) // 64
+    bits = np.zeros((h, groups * 64), dtype=np.uint64)
+    bits[:, :w] = c != 0
+    bits = bits.reshape(h, groups, 32, 2)
+    weights = np.uint64(1) << np.arange(32, dtype=np.uint64)
+    even = (bits[..., 0] * weights).sum(axis=2, dtype=np.uint64)
+    odd = (bits[..., 1] * weights).sum(axis=2, dtype=np.uint64)
+    with np.errstate(over="ignore"):
+        t = (np.arange(h, dtype=np.uint64) * np.uint64(0x9E3779B1)) & _M32
+        a0 = (((t ^ (t >> np.uint64(15))) << np.uint64(1)) | np.uint64(1)) & _M32
+        a1 = (a0 + np.uint64(0x6A09E666)) & _M32
+        k = (np.arange(groups, dtype=np.uint64) + np.uint64(0x7F4A7C15)) & _M32
+        k ^= k >> np.uint64(16)
+        k = (k * np.uint64(0x85EBCA6B)) & _M32
+        k ^= k >> np.uint64(13)
+        k = (k * np.uint64(0xC2B2AE35)) & _M32
+        k ^= k >> np.uint64(16)
+        k |= np.uint64(1)
+        terms = (even * a0[:, None] + odd * a1[:, None]) * k[None, :]
+        return int(terms.sum(dtype=np.uint64))
+
+
+def _trimmed(pattern) -> np.ndarray:
+    """A pattern's cells without its dead outer rows and columns ([0][0] if none lives)."""
+    c = as_cells(pattern)
+    ys, xs = np.nonzero(c)
+    if ys.size == 0:
+        return np.zeros((0, 0), dtype=np.uint8)
+    return c[ys.min():ys.max() + 1, xs.min():xs.max() + 1]
+
+
+def object_hash(pattern) -> int:
+    """The key GolBatch.objects gives an object with these cells: the state
+    hash of the pattern with the corner of its bounding box at cell (0, 0)
+    (what GolBatch.hashes / GolEngine.hash() return for a board holding only
+    it there, whatever the board's size).  `pattern` is any form as_cells
+    takes; dead outer rows and columns do not count."""
+    return _hash_cells(_trimmed(pattern))
+
+
+def _axis_span(occupied: np.ndarray, torus: bool, reach: int) -> tuple[int, int]:
+    """(start, extent) of an object on one axis from its occupied positions
+    (bool [n], some true).  Clipped: minimum and maximum.  Torus: the box
+    starts at the one occupied position whose `reach` cyclic predecessors are
+    all empty and ends at the last occupied one before that gap; without such
+    a position the object goes round the axis: (0, n)."""
+    n = occupied.size
+    if not torus:
+        at = np.flatnonzero(occupied)
+        return int(at[0]), int(at[-1] - at[0] + 1)
+    start = occupied.copy()
+    for k in range(1, reach + 1):
+        start &= ~np.roll(occupied, k)
+    at = np.flatnonzero(start)
+    if at.size == 0:
+        return 0, n
+    s = int(at[0])
+    return s, int(np.flatnonzero(np.roll(occupied, -s))[-1]) + 1
+
+
+def label_objects(cells, torus: bool = True, reach: int = 1) -> np.ndarray:
+    """The objects of one uint8 [H][W] board (H, W <= 64) on the host: the
+    records GolBatch.objects gives for it (OBJECT_DTYPE [n], every object, in
+    its order).  Two live cells are linked iff their Chebyshev distance, cyclic
+    on a torus, is at most `reach` (1 or 2); an object is a connected
+    component.  Labels spread as minima: every live cell starts with its
+    row-major index and takes the smallest label within `reach` until nothing
+    changes, so an object's label is its first cell and sorting the labels
+    gives the order."""
+    c = np.asarray(cells) != 0
+    if c.ndim != 2 or not 1 <= c.shape[0] <= 64 or not 1 <= c.shape[1] <= 64:
+        raise ValueError(f"label_objects takes one [H][W] board of at most 64 x 64 cells, not {c.shape}")
+    if reach not in (1, 2):
+        raise ValueError(f"reach must be 1 or 2, not {reach!r}")
+    H, W = c.shape
+    none = H * W
+
+    def shifted(a, s, axis):  # a moved by s along axis; clipped: `none` comes in
+        if torus:
+            return np.roll(a, s, axis)
+        out = np.full_like(a, none)
+        src = [slice(None)] * 2
+        dst = [slice(None)] * 2
+        src[axis] = slice(0, a.shape[axis] - s) if s > 0 else slice(-s, None)
+        dst[axis] = slice(s, None) if s > 0 else slice(0, a.shape[axis] + s)
+        out[tuple(dst)] = a[tuple(src)]
+        return out
+
+    lab = np.where(c, np.arange(none, dtype=np.int32).reshape(H, W), none).astype(np.int32)
+    while True:
+        m = lab
+        for axis in (0, 1):  # the square window, an axis at a time
+            acc = m
+            for d in range(1, min(reach, m.shape[axis] - 1) + 1):
+                acc = np.minimum(acc, np.minimum(shifted(m, d, axis), shifted(m, -d, axis)))
+            m = acc
+        m = np.where(c, m, none)
+        if np.array_equal(m, lab):
+            break
+        lab = m
+    labels = np.unique(lab[c])
+    out = np.zeros(labels.size, dtype=OBJECT_DTYPE)
+    for rec, label in zip(out, labels):
+        own = lab == label
+        x, w = _axis_span(own.any(axis=0), torus, reach)
+        y, h = _axis_span(own.any(axis=1), torus, reach)
+        moved = np.roll(own, (-y, -x), (0, 1))  # plain on a clipped board: nothing of the object is before its corner
+        rec["hash"] = _hash_cells(moved)
+        rec["x"], rec["y"], rec["w"], rec["h"] = x, y, w, h
+        rec["population"] = int(own.sum())
+    return out
+
+
+def object_table(named) -> dict:
+    """{name: [pattern, ...]} -> {(hash, w, h, population): name}: the keys of
+    GolBatch.objects' records for every distinct orientation (orientations) of
+    every listed image, for batch.tally.  The caller lists an oscillator's
+    phases.  ValueError if two names claim one key."""
+    table: dict = {}
+    for name, images in named.items():
+        for image in images:
+            for cells, _ in orientations(_trimmed(image)):
+                key = (object_hash(cells), cells.shape[1], cells.shape[0], int(cells.sum()))
+                if table.setdefault(key, name) != name:
+                    raise ValueError(f"{name!r} and {table[key]!r} share an image")
+    return table

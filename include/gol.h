@@ -62,7 +62,9 @@ extern "C" {
  * gol_batch_step, gol_batch_hashes, gol_batch_epoch, gol_batch_set_chunk), and
  * its cycle detection (gol_cycle_step, gol_cycle_snapshot_generation,
  * gol_cycle_stats) and its pattern search (gol_find_batch_check,
- * gol_find_batch, gol_find_batch_set_cut, gol_find_batch_stats). */
+ * gol_find_batch, gol_find_batch_set_cut, gol_find_batch_stats) and its
+ * objects (gol_objects_batch_check, gol_objects_batch,
+ * gol_objects_batch_stats). */
 #define GOL_ABI_VERSION 2
 
 /* Return codes. */
@@ -694,6 +696,75 @@ int gol_find_batch_set_cut(gol_batch* batch, uint32_t cared_cells_per_launch);
 /* The last gol_find_batch call of this batch: its launches and the cared cells
  * of its patterns (0 before the first call).  Either pointer may be NULL. */
 int gol_find_batch_stats(gol_batch* batch, uint64_t* launches, uint64_t* cared_cells);
+
+/* The objects of a batch's boards: what a soup census
+ * starts from -- every board cut into its objects, each with a canonical key
+ * -- answered on the device for every board at once.  gol_find_batch counts
+ * the patterns it is given; this says what else the ash holds, how many
+ * distinct objects a board has and where the unfamiliar ones are.  The names
+ * are gol_objects_batch*: the handle is the batch, the capability its own.
+ *
+ * Objects.  Two live stored cells of a board are linked iff their Chebyshev
+ * distance is at most `reach` (1 or 2): cyclic in both directions on
+ * GOL_TORUS, plain on GOL_REF_CLIPPED, where the stored cells outside the
+ * visible extent are cells like any other (as for gol_find_batch).  An object
+ * is a connected component of the link graph.  reach = 1 is 8-connectivity,
+ * reach = 2 groups islands that can influence a common cell.  What
+ * gol_find_batch finds of a pattern inside `reach` rings of cared dead cells
+ * is an object with the pattern's record; the search also wants the rings'
+ * corners dead, which are further than `reach` from an object that does not
+ * fill the corners of its box.
+ *
+ * Order.  A board's objects are numbered by their first cell in row-major
+ * order of plain stored coordinates (smallest y, then smallest x).
+ *
+ * Bounding box.  Clipped: the plain minimum and maximum.  Torus, per axis: the
+ * object's occupied columns (rows) leave at most one cyclic run of at least
+ * `reach` empty columns -- two would disconnect it.  With such a run, x is the
+ * column after it and w is width minus its length; without, the object goes
+ * round the axis: x = 0, w = width.  So w == width on a torus always means
+ * "goes round".
+ *
+ * Hash.  The state hash (gol_hash, gol_batch_hashes) of the object translated
+ * so that its box corner is cell (0, 0), cyclically on a torus and by 0 on an
+ * axis it goes round: what gol_batch_hashes returns for a board that holds
+ * only the object at its corner, whatever the board's size.
+ *
+ * counts_out: [count] -- entry [b - first] is the exact number of objects of
+ * board b (at most 1024: two live cells of one 2 x 2 tile are always linked).
+ * objects_out: [count][max_objects] -- entry [(b - first) * max_objects + j] is
+ * object j of board b for j < min(its count, max_objects); the records past
+ * that are all-zero (a real object has population >= 1).  The capacities are
+ * sizes in entries.  first and count select boards as in gol_batch_hashes.
+ *
+ * gol_objects_batch synchronises and changes neither the boards, the epoch,
+ * the hashes nor anything a later gol_batch_step, gol_cycle_step or
+ * gol_find_batch reads (the plane settle and cycle detection keep is not
+ * written).  The device buffers (counts, records) belong to the handle and
+ * grow on demand (GOL_ENOMEM, and nothing written, if they cannot);
+ * gol_batch_geometry_get's device_bytes is what gol_batch_create allocates, as
+ * before.  NULL arguments, reach outside {1, 2}, max_objects outside
+ * 1 .. 1024, a board range outside the batch and a short capacity return
+ * GOL_EINVAL with a message before any device work and leave both outputs
+ * untouched.  gol_objects_batch_check validates the same arguments for a
+ * geometry and needs no device (as gol_batch_geometry_get). */
+typedef struct gol_batch_object {      /* 16 bytes */
+    uint64_t hash;                     /* translation-invariant key, above */
+    uint8_t  x, y;                     /* bounding-box corner, stored coordinates */
+    uint8_t  w, h;                     /* bounding-box extents, 1 .. 64 */
+    uint16_t population;               /* live cells of the object, 1 .. 4096 */
+    uint16_t reserved;                 /* 0 */
+} gol_batch_object;
+int gol_objects_batch_check(const gol_batch_config* cfg, int64_t first, int64_t count,
+                            int32_t reach, int32_t max_objects);
+int gol_objects_batch(gol_batch* batch, int64_t first, int64_t count, int32_t reach, int32_t max_objects,
+                      uint32_t* counts_out, size_t counts_capacity,
+                      gol_batch_object* objects_out, size_t objects_capacity);
+
+/* The last gol_objects_batch call of this batch: its launches, the objects it
+ * found in all (the sum of its counts) and the boards whose count exceeded
+ * max_objects (0 before the first call).  Any pointer may be NULL. */
+int gol_objects_batch_stats(gol_batch* batch, uint64_t* launches, uint64_t* objects, uint64_t* boards_truncated);
 
 /* Kernel timing: when enabled, the dominant step-kernel launch of every pass
  * (the whole shard, or a sharded shard's interior rows) is bracketed by HIP
