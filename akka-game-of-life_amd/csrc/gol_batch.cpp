@@ -1,8 +1,9 @@
 // gol_batch.cpp -- C ABI of the batch engine (include/gol.h gol_batch_*,
-// gol_cycle_*, gol_find_batch* and gol_objects_batch*; DESIGN.md sections 5f
-// to 5i): many independent boards of at most 64 x 64 stored cells stepped by
-// one launch (kernels: gol_batch.hip), searched by one (gol_batch_find.hip)
-// and cut into their objects by one (gol_batch_objects.hip).  A
+// gol_cycle_*, gol_find_batch*, gol_objects_batch* and gol_census_batch*;
+// DESIGN.md sections 5f to 5j): many independent boards of at most 64 x 64
+// stored cells stepped by one launch (kernels: gol_batch.hip), searched by one
+// (gol_batch_find.hip), cut into their objects by one (gol_batch_objects.hip)
+// and those tallied by one (gol_batch_census.hip).  A
 // handle type of its own: it shares the error conventions and the HIP status
 // discipline with the contexts (gol_ctx.h), and nothing else -- no planner, no
 // step kernel.
@@ -56,6 +57,16 @@ struct gol_batch {
     size_t obj_records_n = 0;
     // gol_objects_batch_stats: the last gol_objects_batch call
     uint64_t obj_launches = 0, obj_total = 0, obj_truncated = 0;
+    // gol_census_batch_*'s table (census_capacity slots, 0: no census has begun) and counters, the calls since
+    // begin, and the buffers, grown on demand, add_records' records and read's entries pass through
+    unsigned long long* census_slots = nullptr;
+    unsigned long long* census_counters = nullptr;
+    uint32_t census_capacity = 0;
+    uint64_t census_calls = 0;
+    gol_batch_object* census_in = nullptr;
+    size_t census_in_n = 0;
+    gol_census_entry* census_out = nullptr;
+    size_t census_out_n = 0;
     std::string err;
 };
 
@@ -105,7 +116,8 @@ void destroy_impl(gol_batch* b) {
     if (b->stream) hip_note(hipStreamSynchronize(b->stream), "batch destroy: hipStreamSynchronize");
     for (void* p : {(void*)b->plane, (void*)b->prev, (void*)b->settled, (void*)b->series, (void*)b->hashes,
                     (void*)b->hash_pops, (void*)b->cycle_words, b->find_table, (void*)b->find_counts,
-                    (void*)b->find_matches, (void*)b->obj_counts, (void*)b->obj_records})
+                    (void*)b->find_matches, (void*)b->obj_counts, (void*)b->obj_records, (void*)b->census_slots,
+                    (void*)b->census_counters, (void*)b->census_in, (void*)b->census_out})
         if (p) hip_note(hipFree(p), "batch destroy: hipFree");
     if (b->stream) hip_note(hipStreamDestroy(b->stream), "batch destroy: hipStreamDestroy");
     delete b;
@@ -133,6 +145,45 @@ bool grow(T*& buf, size_t& have, size_t want, size_t elem) {
 int find_refusal(gol_batch* b, const char* fn, const char* why, int32_t which) {
     if (which >= 0) return batch_err(b, GOL_EINVAL, "%s: pattern %d: %s", fn, which, why);
     return batch_err(b, GOL_EINVAL, "%s: %s", fn, why);
+}
+
+// The objects launch of every board into the handle's buffers, as gol_objects_batch issues it (no copy back, no
+// synchronisation).  GOL_ENOMEM if the buffers cannot be had.
+int launch_objects(gol_batch* batch, const char* fn, int64_t first, int64_t count, int32_t reach,
+                   int32_t max_objects) {
+    const size_t n = (size_t)count, records_n = n * (size_t)max_objects;  // <= 2^22 * 2^10
+    if (!grow(batch->obj_counts, batch->obj_counts_n, n, sizeof(uint32_t)) ||
+        !grow(batch->obj_records, batch->obj_records_n, records_n, sizeof(gol_batch_object)))
+        return batch_err(batch, GOL_ENOMEM, "%s: hipMalloc of the counts (%zu entries) or the records "
+                         "(%zu entries) failed; nothing written", fn, n, records_n);
+    // the records past a board's count are zero: one memset before the launch, the kernel stores the real ones only
+    BATCH_HIP(batch, hipMemsetAsync(batch->obj_records, 0, records_n * sizeof(gol_batch_object), batch->stream));
+    golbatch::ObjectsParams p{};
+    p.plane = batch->plane;
+    p.counts = batch->obj_counts;
+    p.objects = reinterpret_cast<uint4*>(batch->obj_records);
+    p.boards = (int32_t)(first + count);
+    p.width = batch->geo.width;
+    p.height = batch->geo.height;
+    p.boards_per_wave = batch->lanes.boards_per_wave;
+    p.vis_w = batch->geo.vis_w;
+    p.vis_h = batch->geo.vis_h;
+    p.first = (int32_t)first;
+    p.reach = reach;
+    p.max_objects = max_objects;
+    BATCH_HIP(batch, golbatch::launch_batch_objects(p, batch->geo.clipped, batch->stream));
+    return GOL_OK;
+}
+
+golbatch::CensusTable census_table(const gol_batch* b) {
+    return {b->census_slots, b->census_counters, b->census_capacity};
+}
+
+// batch_census_args for a call of this handle: the request's handle fields filled in
+const char* census_refusal(const gol_batch* b, golbatch::CensusRequest r) {
+    r.begun = b->census_capacity != 0;
+    r.next_call = b->census_calls;
+    return golbatch::batch_census_args(b->geo, r);
 }
 
 }  // namespace
@@ -554,26 +605,7 @@ int gol_objects_batch(gol_batch* batch, int64_t first, int64_t count, int32_t re
                          "objects need %zu", objects_capacity, n, max_objects, records_n);
 
     BATCH_HIP(batch, hipSetDevice(batch->device));
-    if (!grow(batch->obj_counts, batch->obj_counts_n, n, sizeof(uint32_t)) ||
-        !grow(batch->obj_records, batch->obj_records_n, records_n, sizeof(gol_batch_object)))
-        return batch_err(batch, GOL_ENOMEM, "gol_objects_batch: hipMalloc of the counts (%zu entries) or the records "
-                         "(%zu entries) failed; nothing written", n, records_n);
-    // the records past a board's count are zero: one memset before the launch, the kernel stores the real ones only
-    BATCH_HIP(batch, hipMemsetAsync(batch->obj_records, 0, records_n * sizeof(gol_batch_object), batch->stream));
-    golbatch::ObjectsParams p{};
-    p.plane = batch->plane;
-    p.counts = batch->obj_counts;
-    p.objects = reinterpret_cast<uint4*>(batch->obj_records);
-    p.boards = (int32_t)(first + count);
-    p.width = batch->geo.width;
-    p.height = batch->geo.height;
-    p.boards_per_wave = batch->lanes.boards_per_wave;
-    p.vis_w = batch->geo.vis_w;
-    p.vis_h = batch->geo.vis_h;
-    p.first = (int32_t)first;
-    p.reach = reach;
-    p.max_objects = max_objects;
-    BATCH_HIP(batch, golbatch::launch_batch_objects(p, batch->geo.clipped, batch->stream));
+    if (const int rc = launch_objects(batch, "gol_objects_batch", first, count, reach, max_objects)) return rc;
     BATCH_HIP(batch, hipMemcpyAsync(counts_out, batch->obj_counts, n * sizeof(uint32_t), hipMemcpyDeviceToHost,
                                     batch->stream));
     BATCH_HIP(batch, hipMemcpyAsync(objects_out, batch->obj_records, records_n * sizeof(gol_batch_object),
@@ -593,6 +625,180 @@ int gol_objects_batch_stats(gol_batch* batch, uint64_t* launches, uint64_t* obje
     if (launches) *launches = batch->obj_launches;
     if (objects) *objects = batch->obj_total;
     if (boards_truncated) *boards_truncated = batch->obj_truncated;
+    return GOL_OK;
+}
+
+int gol_census_batch_check(const gol_batch_config* cfg, int32_t reach, int32_t max_objects, int64_t max_keys) {
+    if (!cfg) return batch_err(nullptr, GOL_EINVAL, "gol_census_batch_check: null configuration");
+    golbatch::Geometry g;
+    if (const char* why = golbatch::batch_geometry(*cfg, &g))
+        return batch_err(nullptr, GOL_EINVAL, "batch of %d boards %d x %d: %s", cfg->boards, cfg->width, cfg->height,
+                         why);
+    golbatch::CensusRequest r{};
+    r.call = golbatch::CensusRequest::kCheck;
+    r.reach = reach;
+    r.max_objects = max_objects;
+    r.max_keys = max_keys;
+    if (const char* why = golbatch::batch_census_args(g, r))
+        return batch_err(nullptr, GOL_EINVAL, "gol_census_batch_check: %s (reach %d, max_objects %d, max_keys %lld)",
+                         why, reach, max_objects, (long long)max_keys);
+    return GOL_OK;
+}
+
+int gol_census_batch_begin(gol_batch* batch, int64_t max_keys) {
+    static_assert(sizeof(gol_census_entry) == 2 * sizeof(uint4), "an entry is two 16-byte stores, and a slot's size");
+    if (!batch) return batch_err(nullptr, GOL_EINVAL, "gol_census_batch_begin: null handle");
+    golbatch::CensusRequest r{};
+    r.call = golbatch::CensusRequest::kBegin;
+    r.max_keys = max_keys;
+    if (const char* why = census_refusal(batch, r))
+        return batch_err(batch, GOL_EINVAL, "gol_census_batch_begin: %s (max_keys %lld)", why, (long long)max_keys);
+    const uint32_t capacity = golbatch::census_capacity(max_keys);
+    BATCH_HIP(batch, hipSetDevice(batch->device));
+    // what is missing is allocated before anything of the handle changes
+    void* slots = nullptr;
+    void* counters = nullptr;
+    const size_t bytes = (size_t)capacity * sizeof(gol_census_entry);
+    if ((capacity != batch->census_capacity && hipMalloc(&slots, bytes) != hipSuccess) ||
+        (!batch->census_counters &&
+         hipMalloc(&counters, golbatch::kCensusCounters * sizeof(unsigned long long)) != hipSuccess)) {
+        (void)hipGetLastError();
+        if (slots) hip_note(hipFree(slots), "gol_census_batch_begin: hipFree");
+        return batch_err(batch, GOL_ENOMEM, "gol_census_batch_begin: hipMalloc of %zu bytes for a table of %u slots "
+                         "failed; nothing changed", bytes, capacity);
+    }
+    if (counters) batch->census_counters = static_cast<unsigned long long*>(counters);
+    if (slots) {  // nothing is in flight on the old table: every call synchronises
+        if (batch->census_slots) hip_note(hipFree(batch->census_slots), "gol_census_batch_begin: hipFree");
+        batch->census_slots = static_cast<unsigned long long*>(slots);
+        batch->census_capacity = capacity;
+    }
+    batch->census_calls = 0;
+    BATCH_HIP(batch, golbatch::launch_census_clear(census_table(batch), batch->stream));
+    BATCH_HIP(batch, hipStreamSynchronize(batch->stream));
+    return GOL_OK;
+}
+
+int gol_census_batch_add(gol_batch* batch, int32_t reach, int32_t max_objects, uint32_t* call_out) {
+    if (!batch) return batch_err(nullptr, GOL_EINVAL, "gol_census_batch_add: null handle");
+    golbatch::CensusRequest r{};
+    r.call = golbatch::CensusRequest::kAdd;
+    r.reach = reach;
+    r.max_objects = max_objects;
+    if (const char* why = census_refusal(batch, r))
+        return batch_err(batch, GOL_EINVAL, "gol_census_batch_add: %s (reach %d, max_objects %d)", why, reach,
+                         max_objects);
+    BATCH_HIP(batch, hipSetDevice(batch->device));
+    if (const int rc = launch_objects(batch, "gol_census_batch_add", 0, batch->geo.boards, reach, max_objects))
+        return rc;
+    golbatch::CensusTallyParams p{};
+    p.records = reinterpret_cast<const uint4*>(batch->obj_records);
+    p.counts = batch->obj_counts;
+    p.table = census_table(batch);
+    p.total = (uint64_t)batch->geo.boards * (uint64_t)max_objects;
+    p.max_objects = (uint32_t)max_objects;
+    p.call = (uint32_t)batch->census_calls;
+    BATCH_HIP(batch, golbatch::launch_census_tally(p, batch->stream));
+    BATCH_HIP(batch, hipStreamSynchronize(batch->stream));
+    if (call_out) *call_out = p.call;
+    ++batch->census_calls;
+    return GOL_OK;
+}
+
+int gol_census_batch_add_records(gol_batch* batch, const gol_batch_object* records, size_t n, uint32_t board,
+                                 uint32_t* call_out) {
+    if (!batch) return batch_err(nullptr, GOL_EINVAL, "gol_census_batch_add_records: null handle");
+    golbatch::CensusRequest r{};
+    r.call = golbatch::CensusRequest::kAddRecords;
+    r.records_null = records == nullptr;
+    r.n = n;
+    r.board = board;
+    if (const char* why = census_refusal(batch, r))
+        return batch_err(batch, GOL_EINVAL, "gol_census_batch_add_records: %s (n %zu, board %u)", why, n, board);
+    const uint32_t call = (uint32_t)batch->census_calls;
+    if (n > 0) {
+        BATCH_HIP(batch, hipSetDevice(batch->device));
+        if (!grow(batch->census_in, batch->census_in_n, n, sizeof(gol_batch_object)))
+            return batch_err(batch, GOL_ENOMEM, "gol_census_batch_add_records: hipMalloc for %zu records failed; "
+                             "nothing tallied", n);
+        // `records` outlives the copy: the call synchronises before it returns
+        BATCH_HIP(batch, hipMemcpyAsync(batch->census_in, records, n * sizeof(gol_batch_object), hipMemcpyHostToDevice,
+                                        batch->stream));
+        golbatch::CensusTallyParams p{};
+        p.records = reinterpret_cast<const uint4*>(batch->census_in);
+        p.table = census_table(batch);
+        p.total = n;
+        p.board = board;
+        p.call = call;
+        BATCH_HIP(batch, golbatch::launch_census_tally(p, batch->stream));
+        BATCH_HIP(batch, hipStreamSynchronize(batch->stream));
+    }
+    if (call_out) *call_out = call;
+    ++batch->census_calls;
+    return GOL_OK;
+}
+
+int gol_census_batch_read(gol_batch* batch, gol_census_entry* entries_out, size_t capacity, size_t* n_out) {
+    if (!batch) return batch_err(nullptr, GOL_EINVAL, "gol_census_batch_read: null handle");
+    golbatch::CensusRequest r{};
+    r.call = golbatch::CensusRequest::kRead;
+    if (const char* why = census_refusal(batch, r)) return batch_err(batch, GOL_EINVAL, "gol_census_batch_read: %s", why);
+    if (!n_out) return batch_err(batch, GOL_EINVAL, "gol_census_batch_read: n_out is null");
+    BATCH_HIP(batch, hipSetDevice(batch->device));
+    unsigned long long counters[golbatch::kCensusCounters];
+    BATCH_HIP(batch, hipMemcpyAsync(counters, batch->census_counters, sizeof counters, hipMemcpyDeviceToHost,
+                                    batch->stream));
+    BATCH_HIP(batch, hipStreamSynchronize(batch->stream));
+    const size_t n = (size_t)counters[golbatch::kCensusDistinct];
+    *n_out = n;
+    if (capacity < n || (n > 0 && !entries_out))
+        return batch_err(batch, GOL_EINVAL, "gol_census_batch_read: entries_out holds %zu entries, the census has %zu "
+                         "distinct keys", entries_out ? capacity : (size_t)0, n);
+    if (n == 0) return GOL_OK;
+    if (!grow(batch->census_out, batch->census_out_n, n, sizeof(gol_census_entry)))
+        return batch_err(batch, GOL_ENOMEM, "gol_census_batch_read: hipMalloc for %zu entries failed; nothing written",
+                         n);
+    BATCH_HIP(batch, hipMemsetAsync(batch->census_counters + golbatch::kCensusCompacted, 0, sizeof(unsigned long long),
+                                    batch->stream));
+    BATCH_HIP(batch, golbatch::launch_census_compact(census_table(batch), reinterpret_cast<uint4*>(batch->census_out),
+                                                     n, batch->stream));
+    std::vector<gol_census_entry> got(n);
+    unsigned long long compacted = 0;
+    BATCH_HIP(batch, hipMemcpyAsync(got.data(), batch->census_out, n * sizeof(gol_census_entry), hipMemcpyDeviceToHost,
+                                    batch->stream));
+    BATCH_HIP(batch, hipMemcpyAsync(&compacted, batch->census_counters + golbatch::kCensusCompacted, sizeof compacted,
+                                    hipMemcpyDeviceToHost, batch->stream));
+    BATCH_HIP(batch, hipStreamSynchronize(batch->stream));
+    if (compacted != n)
+        return batch_err(batch, GOL_ESTATE, "gol_census_batch_read: the table holds %llu occupied slots, its counter "
+                         "says %zu distinct keys; nothing written", compacted, n);
+    std::sort(got.begin(), got.end(), [](const gol_census_entry& a, const gol_census_entry& b) {
+        if (a.count != b.count) return a.count > b.count;
+        if (a.hash != b.hash) return a.hash < b.hash;
+        if (a.w != b.w) return a.w < b.w;
+        if (a.h != b.h) return a.h < b.h;
+        return a.population < b.population;
+    });
+    std::copy(got.begin(), got.end(), entries_out);
+    return GOL_OK;
+}
+
+int gol_census_batch_stats(gol_batch* batch, uint64_t* calls, uint64_t* seen, uint64_t* tallied, uint64_t* truncated,
+                           uint64_t* overflowed, uint64_t* distinct) {
+    if (!batch) return batch_err(nullptr, GOL_EINVAL, "gol_census_batch_stats: null handle");
+    unsigned long long counters[golbatch::kCensusCounters] = {};
+    if (batch->census_capacity != 0) {
+        BATCH_HIP(batch, hipSetDevice(batch->device));
+        BATCH_HIP(batch, hipMemcpyAsync(counters, batch->census_counters, sizeof counters, hipMemcpyDeviceToHost,
+                                        batch->stream));
+        BATCH_HIP(batch, hipStreamSynchronize(batch->stream));
+    }
+    if (calls) *calls = batch->census_calls;
+    if (seen) *seen = counters[golbatch::kCensusSeen];
+    if (tallied) *tallied = counters[golbatch::kCensusTallied];
+    if (truncated) *truncated = counters[golbatch::kCensusTruncated];
+    if (overflowed) *overflowed = counters[golbatch::kCensusOverflowed];
+    if (distinct) *distinct = counters[golbatch::kCensusDistinct];
     return GOL_OK;
 }
 

@@ -205,4 +205,93 @@ struct ObjectsParams {
 // the kernel indexes safely.
 hipError_t launch_batch_objects(const ObjectsParams& p, bool clipped, hipStream_t stream);
 
+// The census of a batch's objects (gol_census_batch_*):
+// a hash table of the handle's, filled on the device from the records the
+// objects kernel leaves there and summed over as many calls as the caller
+// likes.
+constexpr int64_t kMaxCensusKeys = GOL_CENSUS_BATCH_MAX_KEYS;
+// A key is stored only within this many linear probes of its home slot (or the
+// whole table, if that is smaller): the longest any probe loop runs, and what
+// makes "not found in the window" mean "absent".
+constexpr uint32_t kCensusProbeWindow = 256;
+constexpr uint64_t kMaxCensusRecords = 1ull << 22;  // gol_census_batch_add_records' n
+constexpr uint64_t kMaxCensusCalls = 1ull << 24;    // ordinals 0 .. 2^24 - 1: 24 bits of the exemplar's place
+
+// The table's slots for max_keys distinct keys: the power of two >= 2 * max_keys.
+inline uint32_t census_capacity(int64_t max_keys) {
+    uint32_t c = 2;
+    while ((int64_t)c < 2 * max_keys) c <<= 1;
+    return c;
+}
+
+// One census call as its validator sees it: the call, what the handle holds
+// (ignored by kCheck and kBegin) and the call's own arguments (those of the
+// other calls ignored).
+struct CensusRequest {
+    enum Call { kCheck, kBegin, kAdd, kAddRecords, kRead } call;
+    bool begun;                  // the handle has a table
+    uint64_t next_call;          // the ordinal kAdd / kAddRecords would take
+    int32_t reach, max_objects;  // kCheck, kAdd
+    int64_t max_keys;            // kCheck, kBegin
+    bool records_null;           // kAddRecords
+    uint64_t n;
+    uint32_t board;
+};
+
+// Whether a census call is fine (null) or the reason it is refused.  What
+// gol_census_batch_check reports and every gol_census_batch_* call does first.
+inline const char* batch_census_args(const Geometry& g, const CensusRequest& r) {
+    using R = CensusRequest;
+    if (r.call == R::kCheck || r.call == R::kAdd)
+        if (const char* why = batch_objects_args(g, 0, g.boards, r.reach, r.max_objects)) return why;
+    if ((r.call == R::kCheck || r.call == R::kBegin) && (r.max_keys < 1 || r.max_keys > kMaxCensusKeys))
+        return "max_keys must be 1 .. 2^20";
+    if ((r.call == R::kAdd || r.call == R::kAddRecords || r.call == R::kRead) && !r.begun)
+        return "no census has begun (gol_census_batch_begin)";
+    if (r.call == R::kAddRecords) {
+        if (r.n > kMaxCensusRecords) return "n must be at most 2^22";
+        if (r.n > 0 && r.records_null) return "records is null";
+        if (r.board >= (uint32_t)kMaxBoards) return "board must be below 2^22";
+    }
+    if ((r.call == R::kAdd || r.call == R::kAddRecords) && r.next_call >= kMaxCensusCalls)
+        return "the census has had 2^24 calls: ordinals stop at 2^24 - 1 (begin again)";
+    return nullptr;
+}
+
+// The table on the device.  A slot is four qwords: the key's two tagged words
+// A and B (zero: not yet set), the count, and the exemplar's place (all-ones:
+// none yet).  counters: kCensusCounters qwords.
+enum CensusCounter {
+    kCensusSeen, kCensusTallied, kCensusTruncated, kCensusOverflowed, kCensusDistinct,
+    kCensusCompacted,  // the compaction's output offset
+    kCensusCounters
+};
+struct CensusTable {
+    unsigned long long* slots;     // [capacity][4]
+    unsigned long long* counters;  // [kCensusCounters]
+    uint32_t capacity;             // a power of two, 2 .. 2^21
+};
+
+// One tally launch: record slot i < total of `records`.  counts != null (the
+// batch's objects): slot i is record i % max_objects of board i / max_objects,
+// real iff that is below counts[board] and its population is not 0.  counts ==
+// null (the caller's records): every slot is board `board`'s, real iff its
+// population is not 0.
+struct CensusTallyParams {
+    const uint4* records;
+    const uint32_t* counts;
+    CensusTable table;
+    uint64_t total;  // <= 2^32: a slot's index fits 32 bits
+    uint32_t max_objects, board, call;
+};
+
+// gol_batch_census.hip.  hipErrorInvalidValue for parameters outside what the
+// kernels index safely.  clear: an empty table and zero counters.  compact:
+// the occupied slots as gol_census_entry records to `out` (room for
+// out_capacity of them, at least the distinct keys; in any order), their
+// number added to counters[kCensusCompacted] (zeroed by the caller).
+hipError_t launch_census_clear(const CensusTable& t, hipStream_t stream);
+hipError_t launch_census_tally(const CensusTallyParams& p, hipStream_t stream);
+hipError_t launch_census_compact(const CensusTable& t, uint4* out, uint64_t out_capacity, hipStream_t stream);
+
 }  // namespace golbatch

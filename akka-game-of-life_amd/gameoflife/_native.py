@@ -162,6 +162,26 @@ class GolBatchObject(ctypes.Structure):
 # gol_objects_batch: the most objects a board can have (include/gol.h)
 GOL_OBJECTS_BATCH_MAX = 1024
 
+
+class GolCensusEntry(ctypes.Structure):
+    """gol_census_entry: one key of a batch's census (gol_census_batch_read)."""
+    _fields_ = [
+        ("hash", ctypes.c_uint64),
+        ("w", ctypes.c_uint8),
+        ("h", ctypes.c_uint8),
+        ("population", ctypes.c_uint16),
+        ("first_call", ctypes.c_uint32),
+        ("count", ctypes.c_uint64),
+        ("first_board", ctypes.c_uint32),
+        ("first_x", ctypes.c_uint8),
+        ("first_y", ctypes.c_uint8),
+        ("reserved", ctypes.c_uint16),
+    ]
+
+
+# gol_census_batch_begin: the most distinct keys a census can be begun for (include/gol.h)
+GOL_CENSUS_BATCH_MAX_KEYS = 1 << 20
+
 # gol_find_batch: patterns per call, and the automatic launch cut in cared cells (include/gol.h)
 GOL_FIND_BATCH_MAX_PATTERNS = 256
 GOL_FIND_BATCH_AUTO_CUT = 2048
@@ -268,6 +288,13 @@ _SIGNATURES = {
     "gol_objects_batch": (_c.c_int, [_vp, _c.c_int64, _c.c_int64, _c.c_int32, _c.c_int32, _u32p, _c.c_size_t,
                                      ctypes.POINTER(GolBatchObject), _c.c_size_t]),
     "gol_objects_batch_stats": (_c.c_int, [_vp, _u64p, _u64p, _u64p]),
+    "gol_census_batch_check": (_c.c_int, [ctypes.POINTER(GolBatchConfig), _c.c_int32, _c.c_int32, _c.c_int64]),
+    "gol_census_batch_begin": (_c.c_int, [_vp, _c.c_int64]),
+    "gol_census_batch_add": (_c.c_int, [_vp, _c.c_int32, _c.c_int32, _u32p]),
+    "gol_census_batch_add_records": (_c.c_int, [_vp, ctypes.POINTER(GolBatchObject), _c.c_size_t, _c.c_uint32, _u32p]),
+    "gol_census_batch_read": (_c.c_int, [_vp, ctypes.POINTER(GolCensusEntry), _c.c_size_t,
+                                         ctypes.POINTER(_c.c_size_t)]),
+    "gol_census_batch_stats": (_c.c_int, [_vp, _u64p, _u64p, _u64p, _u64p, _u64p, _u64p]),
 }
 
 

@@ -19,6 +19,10 @@ from .rules import Rule, rule_by_name
 
 # gol_batch_object as a numpy record (N.GolBatchObject's fields in its order, 16 bytes)
 OBJECT_DTYPE = P.OBJECT_DTYPE
+# gol_census_entry as a numpy record (N.GolCensusEntry's fields in its order, 32 bytes)
+CENSUS_DTYPE = np.dtype([("hash", "<u8"), ("w", "u1"), ("h", "u1"), ("population", "<u2"), ("first_call", "<u4"),
+                         ("count", "<u8"), ("first_board", "<u4"), ("first_x", "u1"), ("first_y", "u1"),
+                         ("reserved", "<u2")])
 
 
 class GolBatch:
@@ -235,6 +239,53 @@ class GolBatch:
                                                 ctypes.byref(cut)))
         return {"launches": launches.value, "objects": total.value, "boards_truncated": cut.value}
 
+    def census_begin(self, max_keys: int = 65536) -> None:
+        """Begin, or begin again, a census of this batch's objects on the
+        device (gol_census_batch_begin): an empty table with room for
+        `max_keys` distinct keys (hash, w, h, population), call ordinal 0."""
+        self._chk(N.lib.gol_census_batch_begin(self._h, max_keys))
+
+    def census_add(self, reach: int = 1, max_objects: int = 128) -> int:
+        """Tally the objects every board holds now (what objects(reach,
+        max_objects) would return: the records present, min(count, max_objects)
+        per board) into the census, on the device; nothing comes back but this
+        call's ordinal -- 0, 1, ... since census_begin -- which the entries'
+        first_call refers to.  Changes nothing else."""
+        call = ctypes.c_uint32(0)
+        self._chk(N.lib.gol_census_batch_add(self._h, reach, max_objects, ctypes.byref(call)))
+        return call.value
+
+    def census_add_records(self, records, board: int = 0) -> int:
+        """Tally OBJECT_DTYPE records of the caller's (those with population 0
+        are skipped) as if they were board `board`'s: censuses of other
+        handles, processes or GPUs merged into this one.  Returns the call's
+        ordinal."""
+        recs = np.ascontiguousarray(records, dtype=OBJECT_DTYPE).reshape(-1)
+        call = ctypes.c_uint32(0)
+        self._chk(N.lib.gol_census_batch_add_records(self._h, recs.ctypes.data_as(ctypes.POINTER(N.GolBatchObject)),
+                                                     recs.size, board, ctypes.byref(call)))
+        return call.value
+
+    def census_read(self) -> np.ndarray:
+        """The census so far, CENSUS_DTYPE [distinct keys]: per key its count
+        and its earliest occurrence (first_call, first_board, first_y, first_x:
+        the minimum in that order), sorted by (count descending, hash, w, h,
+        population).  Does not clear the census."""
+        n = ctypes.c_size_t(0)
+        out = np.zeros(self.census_stats()["distinct"], dtype=CENSUS_DTYPE)
+        self._chk(N.lib.gol_census_batch_read(self._h, out.ctypes.data_as(ctypes.POINTER(N.GolCensusEntry)), out.size,
+                                              ctypes.byref(n)))
+        return out[:n.value]
+
+    def census_stats(self) -> dict:
+        """The census since census_begin: its calls, and the objects seen,
+        tallied, truncated (beyond max_objects on their board) and overflowed
+        (no room in the table: begin again with more max_keys), seen = tallied
+        + truncated + overflowed, and the distinct keys."""
+        v = [ctypes.c_uint64(0) for _ in range(6)]
+        self._chk(N.lib.gol_census_batch_stats(self._h, *[ctypes.byref(x) for x in v]))
+        return dict(zip(("calls", "seen", "tallied", "truncated", "overflowed", "distinct"), (x.value for x in v)))
+
     @property
     def epoch(self) -> int:
         e = ctypes.c_uint64(0)
@@ -262,6 +313,17 @@ def tally(counts, objects, table) -> dict:
     for k, c in zip(keys.tolist(), n.tolist()):
         name = table.get(tuple(k))
         out[name] = out.get(name, 0) + c
+    return out
+
+
+def census_names(entries, table) -> dict:
+    """A census GolBatch.census_read returned by name: name -> number of
+    objects, by `table` (patterns.object_table), the keys the table does not
+    name under None -- tally's keys and meaning."""
+    out: dict = {}
+    for e in np.asarray(entries).reshape(-1):
+        name = table.get((int(e["hash"]), int(e["w"]), int(e["h"]), int(e["population"])))
+        out[name] = out.get(name, 0) + int(e["count"])
     return out
 
 

@@ -64,7 +64,9 @@ extern "C" {
  * gol_cycle_stats) and its pattern search (gol_find_batch_check,
  * gol_find_batch, gol_find_batch_set_cut, gol_find_batch_stats) and its
  * objects (gol_objects_batch_check, gol_objects_batch,
- * gol_objects_batch_stats). */
+ * gol_objects_batch_stats) and its census (gol_census_batch_check,
+ * gol_census_batch_begin, gol_census_batch_add, gol_census_batch_add_records,
+ * gol_census_batch_read, gol_census_batch_stats). */
 #define GOL_ABI_VERSION 2
 
 /* Return codes. */
@@ -765,6 +767,93 @@ int gol_objects_batch(gol_batch* batch, int64_t first, int64_t count, int32_t re
  * found in all (the sum of its counts) and the boards whose count exceeded
  * max_objects (0 before the first call).  Any pointer may be NULL. */
 int gol_objects_batch_stats(gol_batch* batch, uint64_t* launches, uint64_t* objects, uint64_t* boards_truncated);
+
+/* The census of a batch's objects: how many of each
+ * object, over all boards and over as many calls (reseeds) as the caller
+ * likes, and one place to look each of them up -- kept in a hash table on the
+ * device that belongs to the handle, filled from the records
+ * gol_objects_batch's kernel leaves in device memory, and read back once as a
+ * short sorted list.  The names are gol_census_batch*.
+ *
+ * Key.  (hash, w, h, population) of a gol_batch_object record.  Every value of
+ * hash is a legal key, 0 and all-ones included.
+ *
+ * gol_census_batch_begin allocates, or clears, a table for max_keys distinct
+ * keys, 1 .. GOL_CENSUS_BATCH_MAX_KEYS: its capacity is the power of two
+ * >= 2 * max_keys, in slots of 32 bytes.  It resets the call ordinal and the
+ * statistics and may be called again at any time.  The table belongs to the
+ * handle, is freed by gol_batch_destroy and is not part of
+ * gol_batch_geometry_get's device_bytes, which stays what gol_batch_create
+ * allocates.  GOL_ENOMEM: nothing is changed -- a census begun before goes on.
+ *
+ * gol_census_batch_add runs the objects launch of gol_objects_batch (reach,
+ * max_objects as there) over all boards at their current state into the
+ * handle's objects buffers, tallies every real record -- j < min(count,
+ * max_objects) of each board -- and synchronises.  It changes nothing that
+ * gol_batch_step, gol_cycle_step, gol_find_batch or gol_objects_batch reads or
+ * returns: boards, epoch, hashes and the plane settle and cycle detection
+ * keep.  *call_out (may be NULL) is this call's ordinal: 0, 1, ... since
+ * begin; the caller keeps ordinal -> seed.  Ordinals stop at 2^24 - 1: the
+ * next add is refused.
+ *
+ * gol_census_batch_add_records tallies n caller-supplied records (n <= 2^22;
+ * those with population 0 are skipped) as if they were board `board`'s
+ * (< 2^22), and takes an ordinal like add: how censuses of other handles,
+ * processes or GPUs are merged (an entry as count records would be too many:
+ * the merge is of what objects calls returned).
+ *
+ * Accounting, exact and always:
+ *     seen = tallied + truncated + overflowed,   sum of entry.count = tallied.
+ * seen: for add the sum of the boards' exact counts, for add_records the
+ * records with a population; truncated: the sum over boards of
+ * max(count - max_objects, 0); overflowed: below.
+ *
+ * Overflow.  A key is stored only within min(capacity, 256) linear probes of
+ * its home slot, so a lookup that does not find it there knows it is absent,
+ * and no probe loop is longer.  An object whose key finds neither itself nor
+ * a free slot there is counted in overflowed and nowhere else.  With distinct
+ * <= max_keys (load <= 0.5) no overflow is expected; beyond that, which keys
+ * are kept is unspecified, and overflowed > 0 tells the caller to begin again
+ * with more room.
+ *
+ * Exemplar.  first_call, first_board, first_y, first_x: the minimum of (call,
+ * board, y, x) over the key's occurrences, x and y the box corner.
+ * Deterministic.
+ *
+ * gol_census_batch_read compacts the occupied slots on the device, copies
+ * them out and sorts them on the host by (count descending, hash, w, h,
+ * population): the output is identical from run to run.  *n_out is the number
+ * of distinct keys; capacity (in entries) below it returns GOL_EINVAL with
+ * *n_out set and entries_out untouched.  It does not clear the census.
+ *
+ * gol_census_batch_stats: the add / add_records calls since begin, and seen,
+ * tallied, truncated, overflowed, distinct as above (zeros before begin).  Any
+ * pointer may be NULL.
+ *
+ * NULL handles, add / add_records / read before begin, reach outside {1, 2},
+ * max_objects outside 1 .. 1024, max_keys outside 1 .. 2^20 and n above 2^22
+ * return GOL_EINVAL with a message before any device work.
+ * gol_census_batch_check validates reach, max_objects and max_keys for a
+ * geometry and needs no device. */
+#define GOL_CENSUS_BATCH_MAX_KEYS (1 << 20)
+typedef struct gol_census_entry {      /* 32 bytes */
+    uint64_t hash;                     /* gol_batch_object.hash */
+    uint8_t  w, h;                     /* its box extents */
+    uint16_t population;
+    uint32_t first_call;               /* ordinal of the add call of the earliest occurrence */
+    uint64_t count;                    /* objects with this key since begin */
+    uint32_t first_board;              /* ... its board, */
+    uint8_t  first_x, first_y;         /* ... its box corner */
+    uint16_t reserved;                 /* 0 */
+} gol_census_entry;
+int gol_census_batch_check(const gol_batch_config* cfg, int32_t reach, int32_t max_objects, int64_t max_keys);
+int gol_census_batch_begin(gol_batch* batch, int64_t max_keys);
+int gol_census_batch_add(gol_batch* batch, int32_t reach, int32_t max_objects, uint32_t* call_out);
+int gol_census_batch_add_records(gol_batch* batch, const gol_batch_object* records, size_t n, uint32_t board,
+                                 uint32_t* call_out);
+int gol_census_batch_read(gol_batch* batch, gol_census_entry* entries_out, size_t capacity, size_t* n_out);
+int gol_census_batch_stats(gol_batch* batch, uint64_t* calls, uint64_t* seen, uint64_t* tallied,
+                           uint64_t* truncated, uint64_t* overflowed, uint64_t* distinct);
 
 /* Kernel timing: when enabled, the dominant step-kernel launch of every pass
  * (the whole shard, or a sharded shard's interior rows) is bracketed by HIP
