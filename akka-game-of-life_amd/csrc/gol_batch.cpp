@@ -1,6 +1,6 @@
 // gol_batch.cpp -- C ABI of the batch engine (include/gol.h gol_batch_*,
-// gol_cycle_*, gol_find_batch*, gol_objects_batch* and gol_census_batch*;
-// DESIGN.md sections 5f to 5j): many independent boards of at most 64 x 64
+// gol_cycle_*, gol_find_batch*, gol_objects_batch*, gol_census_batch* and
+// gol_rules_batch_*; DESIGN.md sections 5f to 5k): many independent boards of at most 64 x 64
 // stored cells stepped by one launch (kernels: gol_batch.hip), searched by one
 // (gol_batch_find.hip), cut into their objects by one (gol_batch_objects.hip)
 // and those tallied by one (gol_batch_census.hip).  A
@@ -67,6 +67,12 @@ struct gol_batch {
     size_t census_in_n = 0;
     gol_census_entry* census_out = nullptr;
     size_t census_out_n = 0;
+    // gol_rules_batch_*: the device's rule words [boards], allocated by the first set; their host copy, the rules
+    // in force (empty before the first set: the configuration's rule everywhere); and whether the steps launch the
+    // RULES instances
+    uint32_t* rules = nullptr;
+    std::vector<uint32_t> rules_host;
+    bool rules_on = false;
     std::string err;
 };
 
@@ -117,7 +123,7 @@ void destroy_impl(gol_batch* b) {
     for (void* p : {(void*)b->plane, (void*)b->prev, (void*)b->settled, (void*)b->series, (void*)b->hashes,
                     (void*)b->hash_pops, (void*)b->cycle_words, b->find_table, (void*)b->find_counts,
                     (void*)b->find_matches, (void*)b->obj_counts, (void*)b->obj_records, (void*)b->census_slots,
-                    (void*)b->census_counters, (void*)b->census_in, (void*)b->census_out})
+                    (void*)b->census_counters, (void*)b->census_in, (void*)b->census_out, (void*)b->rules})
         if (p) hip_note(hipFree(p), "batch destroy: hipFree");
     if (b->stream) hip_note(hipStreamDestroy(b->stream), "batch destroy: hipStreamDestroy");
     delete b;
@@ -173,6 +179,16 @@ int launch_objects(gol_batch* batch, const char* fn, int64_t first, int64_t coun
     p.max_objects = max_objects;
     BATCH_HIP(batch, golbatch::launch_batch_objects(p, batch->geo.clipped, batch->stream));
     return GOL_OK;
+}
+
+// batch_rules_args' refusal as a message: "rules[5] (board 7) = 0x...: ..." or the range
+int rules_refusal(gol_batch* b, const char* fn, const char* why, const golbatch::Geometry& g, int64_t first,
+                  int64_t count, const uint32_t* rules, int64_t which) {
+    if (which >= 0)
+        return batch_err(b, GOL_EINVAL, "%s: rules[%lld] (board %lld) = 0x%08X: %s", fn, (long long)which,
+                         (long long)(first + which), rules[which], why);
+    return batch_err(b, GOL_EINVAL, "%s: %s (first %lld, count %lld, batch of %d)", fn, why, (long long)first,
+                     (long long)count, g.boards);
 }
 
 golbatch::CensusTable census_table(const gol_batch* b) {
@@ -334,10 +350,12 @@ int gol_batch_step(gol_batch* batch, uint32_t generations, uint32_t* populations
     p.pop_stride = (uint32_t)batch->series_gens;
     p.birth = batch->birth;
     p.survive = batch->survive;
+    p.rules = batch->rules_on ? batch->rules : nullptr;
     for (uint32_t g0 = 0; g0 < generations; g0 += chunk) {
         p.gens = std::min(chunk, generations - g0);
         p.g0 = g0;
-        BATCH_HIP(batch, golbatch::launch_batch_step(p, life_rule(batch), batch->geo.clipped, batch->stream));
+        BATCH_HIP(batch, golbatch::launch_batch_step(p, life_rule(batch), batch->geo.clipped, batch->rules_on,
+                                                     batch->stream));
         batch->epoch += p.gens;
         if (populations_out)  // this launch's columns of the caller's [boards][generations]; waits for the launch
             BATCH_HIP(batch, hipMemcpy2DAsync(populations_out + g0, (size_t)generations * sizeof(uint32_t), batch->series,
@@ -388,6 +406,7 @@ int gol_cycle_step(gol_batch* batch, uint32_t generations, uint32_t* period_out,
     p.vis_h = batch->geo.vis_h;
     p.birth = batch->birth;
     p.survive = batch->survive;
+    p.rules = batch->rules_on ? batch->rules : nullptr;
     // the first launch of a call reads neither the words nor the snapshot plane; the counters start at zero
     BATCH_HIP(batch, hipMemsetAsync(p.counters, 0, 2 * sizeof(uint32_t), batch->stream));
     batch->cycle_launches = 0;
@@ -398,7 +417,8 @@ int gol_cycle_step(gol_batch* batch, uint32_t generations, uint32_t* period_out,
         const bool all = counters[0] == boards && counters[1] - 1u <= chunk;
         p.gens = all ? generations - g0 : std::min(chunk, generations - g0);
         p.g0 = g0;
-        BATCH_HIP(batch, golbatch::launch_batch_cycle(p, life_rule(batch), batch->geo.clipped, batch->stream));
+        BATCH_HIP(batch, golbatch::launch_batch_cycle(p, life_rule(batch), batch->geo.clipped, batch->rules_on,
+                                                      batch->stream));
         batch->epoch += p.gens;
         ++batch->cycle_launches;
         BATCH_HIP(batch, hipMemcpyAsync(counters, p.counters, sizeof counters, hipMemcpyDeviceToHost, batch->stream));
@@ -799,6 +819,67 @@ int gol_census_batch_stats(gol_batch* batch, uint64_t* calls, uint64_t* seen, ui
     if (truncated) *truncated = counters[golbatch::kCensusTruncated];
     if (overflowed) *overflowed = counters[golbatch::kCensusOverflowed];
     if (distinct) *distinct = counters[golbatch::kCensusDistinct];
+    return GOL_OK;
+}
+
+int gol_rules_batch_check(const gol_batch_config* cfg, int64_t first, int64_t count, const uint32_t* rules) {
+    if (!cfg) return batch_err(nullptr, GOL_EINVAL, "gol_rules_batch_check: null configuration");
+    golbatch::Geometry g;
+    if (const char* why = golbatch::batch_geometry(*cfg, &g))
+        return batch_err(nullptr, GOL_EINVAL, "batch of %d boards %d x %d: %s", cfg->boards, cfg->width, cfg->height,
+                         why);
+    int64_t which = -1;
+    if (const char* why = golbatch::batch_rules_args(g, first, count, rules, &which))
+        return rules_refusal(nullptr, "gol_rules_batch_check", why, g, first, count, rules, which);
+    return GOL_OK;
+}
+
+int gol_rules_batch_set(gol_batch* batch, int64_t first, int64_t count, const uint32_t* rules) {
+    if (!batch) return batch_err(nullptr, GOL_EINVAL, "gol_rules_batch_set: null handle");
+    int64_t which = -1;
+    if (const char* why = golbatch::batch_rules_args(batch->geo, first, count, rules, &which))
+        return rules_refusal(batch, "gol_rules_batch_set", why, batch->geo, first, count, rules, which);
+    const size_t boards = (size_t)batch->geo.boards;
+    const uint32_t config_word = golbatch::rule_word(batch->birth, batch->survive);
+    if (!rules) {  // the whole batch back to its configuration's rule; the device words stay for a later set
+        batch->rules_on = false;
+        std::fill(batch->rules_host.begin(), batch->rules_host.end(), config_word);
+        return GOL_OK;
+    }
+    BATCH_HIP(batch, hipSetDevice(batch->device));
+    if (!batch->rules) {
+        void* words = nullptr;
+        if (hipMalloc(&words, boards * sizeof(uint32_t)) != hipSuccess) {
+            (void)hipGetLastError();
+            return batch_err(batch, GOL_ENOMEM, "gol_rules_batch_set: hipMalloc of %zu bytes for the rule words failed; "
+                             "nothing changed", boards * sizeof(uint32_t));
+        }
+        batch->rules = static_cast<uint32_t*>(words);
+    }
+    // the device takes a copy of what the rules will be; the handle changes once it has arrived
+    std::vector<uint32_t> next = batch->rules_host;
+    if (next.empty()) next.assign(boards, config_word);
+    std::copy(rules, rules + count, next.begin() + first);
+    // while the configuration's rule is in force the device words are stale (or new): all of them go
+    const size_t lo = batch->rules_on ? (size_t)first : 0, n = batch->rules_on ? (size_t)count : boards;
+    BATCH_HIP(batch, hipMemcpyAsync(batch->rules + lo, next.data() + lo, n * sizeof(uint32_t), hipMemcpyHostToDevice,
+                                    batch->stream));
+    BATCH_HIP(batch, hipStreamSynchronize(batch->stream));
+    batch->rules_host.swap(next);
+    batch->rules_on = true;
+    return GOL_OK;
+}
+
+int gol_rules_batch_get(gol_batch* batch, int64_t first, int64_t count, uint32_t* rules_out) {
+    if (!batch) return batch_err(nullptr, GOL_EINVAL, "gol_rules_batch_get: null handle");
+    if (!rules_out) return batch_err(batch, GOL_EINVAL, "gol_rules_batch_get: rules_out is null");
+    if (!window_ok(batch, first, count))
+        return batch_err(batch, GOL_EINVAL, "gol_rules_batch_get: boards [%lld, %lld + %lld) outside the batch of %d",
+                         (long long)first, (long long)first, (long long)count, batch->geo.boards);
+    if (batch->rules_host.empty())
+        std::fill(rules_out, rules_out + count, golbatch::rule_word(batch->birth, batch->survive));
+    else
+        std::copy(batch->rules_host.begin() + first, batch->rules_host.begin() + first + count, rules_out);
     return GOL_OK;
 }
 

@@ -115,6 +115,31 @@ struct FindParams {
     int32_t npatterns, first, count;
 };
 
+// Per-board rules (gol_rules_batch_*): one word per
+// board, the birth mask in bits 0..8 and the survive mask in bits 16..24
+// (GOL_BATCH_RULE); no other bit may be set.
+constexpr uint32_t kRuleWordBits = 0x01FF01FFu;
+inline uint32_t rule_word(uint32_t birth, uint32_t survive) { return GOL_BATCH_RULE(birth, survive); }
+
+// The rules boards first .. first + count - 1 of a batch of geometry g can be
+// given, or the reason they are refused (null: fine) and, in *which, the index
+// into `rules` of the word it is about (-1: the range).  rules == null (back
+// to the configuration's rule) is for the whole batch only.  What
+// gol_rules_batch_check reports and gol_rules_batch_set does first.
+inline const char* batch_rules_args(const Geometry& g, int64_t first, int64_t count, const uint32_t* rules,
+                                    int64_t* which) {
+    *which = -1;
+    if (first < 0 || count < 1 || first >= g.boards || count > (int64_t)g.boards - first)
+        return "boards [first, first + count) outside the batch";
+    if (!rules) return first == 0 && count == g.boards ? nullptr : "rules is null for a part of the batch";
+    for (int64_t j = 0; j < count; ++j)
+        if (rules[j] & ~kRuleWordBits) {
+            *which = j;
+            return "a rule word has a bit set outside the birth mask (bits 0..8) and the survive mask (bits 16..24)";
+        }
+    return nullptr;
+}
+
 // One launch: `gens` generations of every board, in place.
 struct StepParams {
     unsigned long long* plane;  // boards * height rows
@@ -127,6 +152,7 @@ struct StepParams {
     uint32_t g0;                // generations of the call before this launch
     uint32_t pop_stride;
     uint32_t birth, survive;
+    const uint32_t* rules;      // per-board rules (the RULES instances): [boards] rule words; null: birth / survive
 };
 
 // Cycle detection's schedule (gol_cycle_step): Brent's
@@ -155,13 +181,16 @@ struct CycleParams {
     uint32_t gens;              // generations of this launch
     uint32_t g0;                // generations of the call before this launch
     uint32_t birth, survive;
+    const uint32_t* rules;      // per-board rules (the RULES instances): [boards] rule words; null: birth / survive
 };
 
 // life: the B3/S23 instances; clipped: the topology; null pops / settled: the
-// instance without that part.  hipErrorInvalidValue for parameters outside
-// what the kernels index safely.
-hipError_t launch_batch_step(const StepParams& p, bool life, bool clipped, hipStream_t stream);
-hipError_t launch_batch_cycle(const CycleParams& p, bool life, bool clipped, hipStream_t stream);
+// instance without that part; rules: the RULES instances, every board under
+// its own word of p.rules (`life` means nothing then).  hipErrorInvalidValue
+// for parameters outside what the kernels index safely, and for a p.rules
+// that is null with `rules` or set without it.
+hipError_t launch_batch_step(const StepParams& p, bool life, bool clipped, bool rules, hipStream_t stream);
+hipError_t launch_batch_cycle(const CycleParams& p, bool life, bool clipped, bool rules, hipStream_t stream);
 hipError_t launch_batch_seed(unsigned long long* plane, int64_t words, int32_t width, uint64_t seed,
                              hipStream_t stream);
 // hashes[i] / pops[i] (either may be null) of boards first .. first + count - 1.

@@ -24,6 +24,9 @@
 //                         ballot masked to the board's lanes.
 // The generation itself is gol_batch_gen.h's, shared with batch_cycle_kernel
 // (below: the same loops with cycle detection, early exit and fast-forward).
+// Both kernels have RULES instances: every board under
+// a rule word of its own, scalar masks where a wave is one board, per-lane
+// conditions where it holds several -- the same loop bodies either way.
 // Idle lanes (past k * height, or of boards past the batch) compute along --
 // the loop has no lane branch around a cross-lane operation, so DPP and
 // permutes see every lane -- and contribute to nothing: active lanes never read them (torus) or read them as
@@ -58,8 +61,18 @@ __device__ __forceinline__ uint32_t wave_prefix_sum(uint32_t v) {
     return v;
 }
 
-template <bool LIFE, bool CLIPPED, bool POP, bool SETTLE>
+// The rule a RULES instance hands the generation in p's place (P: birth, survive).
+struct RuleMasks {
+    uint32_t birth, survive;
+};
+__device__ __forceinline__ RuleMasks rule_masks(uint32_t word) { return RuleMasks{word & 0x1FFu, (word >> 16) & 0x1FFu}; }
+
+// RULES: every board under its own rule word,
+// p.rules[board], loaded once before the loop (idle lanes take 0).  LIFE means
+// nothing then: the generic adder runs.
+template <bool LIFE, bool CLIPPED, bool POP, bool SETTLE, bool RULES = false>
 __global__ __launch_bounds__(kLanes* kWavesPerWG) void batch_step_kernel(const StepParams p) {
+    static_assert(!(RULES && LIFE), "the RULES instances are generic");
     const int lane = threadIdx.x & (kLanes - 1);
     const int wave_in_wg = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / kLanes));
     const int32_t wave = (int32_t)blockIdx.x * kWavesPerWG + wave_in_wg;  // waves <= boards <= 2^22
@@ -104,9 +117,11 @@ __global__ __launch_bounds__(kLanes* kWavesPerWG) void batch_step_kernel(const S
 
     Row cur = {0u, 0u}, prev = {0u, 0u};
     uint32_t first = 0u;
+    uint32_t word = 0u;  // RULES: the board's rule
     if (active) {
         const unsigned long long r = p.plane[idx];
         cur = {(uint32_t)r, (uint32_t)(r >> 32)};
+        if constexpr (RULES) word = p.rules[board];
         if constexpr (SETTLE) {
             if (p.g0 > 0) {
                 const unsigned long long q = p.prev[idx];
@@ -116,13 +131,14 @@ __global__ __launch_bounds__(kLanes* kWavesPerWG) void batch_step_kernel(const S
         }
     }
 
-    // the four loops of gol_batch_gen.h's generation: rotates or permutes, wide or narrow
-    auto run = [&](auto ROT_, auto NARROW_) __attribute__((always_inline)) {
+    // the four loops of gol_batch_gen.h's generation: rotates or permutes, wide or narrow; R: the rule (p, or a
+    // RULES instance's masks)
+    auto run = [&](auto ROT_, auto NARROW_, const auto& R) __attribute__((always_inline)) {
         constexpr bool ROT = decltype(ROT_)::value;
         constexpr bool NARROW = decltype(NARROW_)::value;
         if constexpr (NARROW) cur.hi = prev.hi = 0u;
         for (uint32_t g = 0; g < p.gens; ++g) {
-            const Row nx = generation<LIFE, CLIPPED, ROT, NARROW>(p, C, cur);
+            const Row nx = generation<LIFE, CLIPPED, ROT, NARROW>(R, C, cur);
             if constexpr (POP) {
                 const uint32_t bits = (uint32_t)__builtin_popcount(nx.lo) + (NARROW ? 0u : (uint32_t)__builtin_popcount(nx.hi));
                 const uint32_t incl = wave_prefix_sum(active ? bits : 0u);
@@ -140,10 +156,24 @@ __global__ __launch_bounds__(kLanes* kWavesPerWG) void batch_step_kernel(const S
     };
     // wave-uniform, outside the loop
     const bool rot = !CLIPPED && H == kLanes, narrow = p.width <= 32;
-    if (rot && narrow) run(std::true_type{}, std::true_type{});
-    else if (rot) run(std::true_type{}, std::false_type{});
-    else if (narrow) run(std::false_type{}, std::true_type{});
-    else run(std::false_type{}, std::false_type{});
+    if constexpr (!RULES) {  // written out, not shared with the paths below: so these instances keep their code
+        if (rot && narrow) run(std::true_type{}, std::true_type{}, p);
+        else if (rot) run(std::true_type{}, std::false_type{}, p);
+        else if (narrow) run(std::false_type{}, std::true_type{}, p);
+        else run(std::false_type{}, std::false_type{}, p);
+    } else if (p.boards_per_wave == 1) {
+        // the wave is one board (lane 0 is active): one rule, its masks scalar as the uniform generic instances'
+        const RuleMasks R = rule_masks((uint32_t)__builtin_amdgcn_readfirstlane((int)word));
+        if (rot && narrow) run(std::true_type{}, std::true_type{}, R);
+        else if (rot) run(std::true_type{}, std::false_type{}, R);
+        else if (narrow) run(std::false_type{}, std::true_type{}, R);
+        else run(std::false_type{}, std::false_type{}, R);
+    } else {
+        // a rule per board, so per lane (rot needs height 64: the two permute loops); the rule is data, no branch
+        const RuleMasks R = rule_masks(word);
+        if (narrow) run(std::false_type{}, std::true_type{}, R);
+        else run(std::false_type{}, std::false_type{}, R);
+    }
 
     if (active) {
         p.plane[idx] = (unsigned long long)cur.lo | ((unsigned long long)cur.hi << 32);
@@ -166,8 +196,9 @@ __global__ __launch_bounds__(kLanes* kWavesPerWG) void batch_step_kernel(const S
 // where the lane does.  Both loop conditions are ballots or scalars: no lane
 // branch surrounds a DPP or permute.  A wave with an undetected board keeps
 // stepping all its boards, which evolve truthfully.
-template <bool LIFE, bool CLIPPED>
+template <bool LIFE, bool CLIPPED, bool RULES = false>
 __global__ __launch_bounds__(kLanes* kWavesPerWG) void batch_cycle_kernel(const CycleParams p) {
+    static_assert(!(RULES && LIFE), "the RULES instances are generic");
     const int lane = threadIdx.x & (kLanes - 1);
     const int wave_in_wg = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / kLanes));
     const int32_t wave = (int32_t)blockIdx.x * kWavesPerWG + wave_in_wg;  // waves <= boards <= 2^22
@@ -183,10 +214,12 @@ __global__ __launch_bounds__(kLanes* kWavesPerWG) void batch_cycle_kernel(const 
     };
     Row cur = {0u, 0u}, snap = {0u, 0u};
     uint32_t seen = 1u;  // idle lanes: done with period 1, owing nothing
+    uint32_t word = 0u;  // RULES: the board's rule
     if (L.active) {
         const unsigned long long r = p.plane[L.idx];
         cur = {(uint32_t)r, (uint32_t)(r >> 32)};
         seen = p.g0 > 0 ? p.seen[L.board] : 0u;
+        if constexpr (RULES) word = p.rules[L.board];
     }
     const uint32_t seen_in = seen;
     // wave-uniform: some board of the wave has no period yet.  A later launch that finds none goes straight to the
@@ -201,13 +234,13 @@ __global__ __launch_bounds__(kLanes* kWavesPerWG) void batch_cycle_kernel(const 
         }
     }
 
-    auto run = [&](auto ROT_, auto NARROW_) __attribute__((always_inline)) {
+    auto run = [&](auto ROT_, auto NARROW_, const auto& R) __attribute__((always_inline)) {
         constexpr bool ROT = decltype(ROT_)::value;
         constexpr bool NARROW = decltype(NARROW_)::value;
         if constexpr (NARROW) cur.hi = snap.hi = 0u;
         uint32_t g = 0u;  // scalar: generations run
         for (; g < p.gens && open; ++g) {
-            const Row nx = generation<LIFE, CLIPPED, ROT, NARROW>(p, C, cur);
+            const Row nx = generation<LIFE, CLIPPED, ROT, NARROW>(R, C, cur);
             const unsigned long long same =
                 __builtin_amdgcn_ballot_w64(nx.lo == snap.lo && (NARROW || nx.hi == snap.hi));
             const uint32_t gen = p.g0 + g + 1u;  // generation of the call that nx is (<= 2^32 - 1)
@@ -220,7 +253,7 @@ __global__ __launch_bounds__(kLanes* kWavesPerWG) void batch_cycle_kernel(const 
         const uint32_t period = period_of(seen);
         uint32_t left = (p.gens - g) % (period ? period : 1u);
         while (__builtin_amdgcn_ballot_w64(left > 0u) != 0ull) {
-            const Row nx = generation<LIFE, CLIPPED, ROT, NARROW>(p, C, cur);
+            const Row nx = generation<LIFE, CLIPPED, ROT, NARROW>(R, C, cur);
             const bool owes = left > 0u;
             cur.lo = owes ? nx.lo : cur.lo;
             if constexpr (!NARROW) cur.hi = owes ? nx.hi : cur.hi;
@@ -229,10 +262,24 @@ __global__ __launch_bounds__(kLanes* kWavesPerWG) void batch_cycle_kernel(const 
     };
     // wave-uniform, outside the loops
     const bool rot = !CLIPPED && L.H == kLanes, narrow = p.width <= 32;
-    if (rot && narrow) run(std::true_type{}, std::true_type{});
-    else if (rot) run(std::true_type{}, std::false_type{});
-    else if (narrow) run(std::false_type{}, std::true_type{});
-    else run(std::false_type{}, std::false_type{});
+    if constexpr (!RULES) {  // written out, not shared with the paths below: so these instances keep their code
+        if (rot && narrow) run(std::true_type{}, std::true_type{}, p);
+        else if (rot) run(std::true_type{}, std::false_type{}, p);
+        else if (narrow) run(std::false_type{}, std::true_type{}, p);
+        else run(std::false_type{}, std::false_type{}, p);
+    } else if (p.boards_per_wave == 1) {
+        // the wave is one board (lane 0 is active): one rule, its masks scalar as the uniform generic instances'
+        const RuleMasks R = rule_masks((uint32_t)__builtin_amdgcn_readfirstlane((int)word));
+        if (rot && narrow) run(std::true_type{}, std::true_type{}, R);
+        else if (rot) run(std::true_type{}, std::false_type{}, R);
+        else if (narrow) run(std::false_type{}, std::true_type{}, R);
+        else run(std::false_type{}, std::false_type{}, R);
+    } else {
+        // a rule per board, so per lane (rot needs height 64: the two permute loops); the rule is data, no branch
+        const RuleMasks R = rule_masks(word);
+        if (narrow) run(std::false_type{}, std::true_type{}, R);
+        else run(std::false_type{}, std::false_type{}, R);
+    }
 
     if (L.active) {
         p.plane[L.idx] = (unsigned long long)cur.lo | ((unsigned long long)cur.hi << 32);
@@ -285,33 +332,39 @@ __global__ __launch_bounds__(256) void batch_hash_kernel(const unsigned long lon
     if (pops) pops[i] = n;
 }
 
-template <bool LIFE, bool CLIPPED>
+template <bool LIFE, bool CLIPPED, bool RULES = false>
 hipError_t launch_step_flags(const StepParams& p, dim3 grid, hipStream_t stream) {
     const dim3 block(kLanes * kWavesPerWG);
     const bool pop = p.pops != nullptr, settle = p.settled != nullptr;
-    if (pop && settle) return gol::launch_kernel(batch_step_kernel<LIFE, CLIPPED, true, true>, grid, block, stream, p);
-    if (pop) return gol::launch_kernel(batch_step_kernel<LIFE, CLIPPED, true, false>, grid, block, stream, p);
-    if (settle) return gol::launch_kernel(batch_step_kernel<LIFE, CLIPPED, false, true>, grid, block, stream, p);
-    return gol::launch_kernel(batch_step_kernel<LIFE, CLIPPED, false, false>, grid, block, stream, p);
+    if (pop && settle)
+        return gol::launch_kernel(batch_step_kernel<LIFE, CLIPPED, true, true, RULES>, grid, block, stream, p);
+    if (pop) return gol::launch_kernel(batch_step_kernel<LIFE, CLIPPED, true, false, RULES>, grid, block, stream, p);
+    if (settle) return gol::launch_kernel(batch_step_kernel<LIFE, CLIPPED, false, true, RULES>, grid, block, stream, p);
+    return gol::launch_kernel(batch_step_kernel<LIFE, CLIPPED, false, false, RULES>, grid, block, stream, p);
 }
 
 }  // namespace
 
-hipError_t launch_batch_step(const StepParams& p, bool life, bool clipped, hipStream_t stream) {
-    // every index the kernel forms stays inside the plane, the series and the settle words
-    if (!p.plane || p.boards < 1 || p.boards > kMaxBoards || p.width < 1 || p.width > kLanes || p.height < 1 ||
+hipError_t launch_batch_step(const StepParams& p, bool life, bool clipped, bool rules, hipStream_t stream) {
+    // every index the kernel forms stays inside the plane, the series, the settle words and the rule words
+    if (rules != (p.rules != nullptr) ||
+        !p.plane || p.boards < 1 || p.boards > kMaxBoards || p.width < 1 || p.width > kLanes || p.height < 1 ||
         p.height > kLanes || p.boards_per_wave != batch_lanes(p.height, p.boards).boards_per_wave || p.gens < 1 ||
         (p.pops && p.pop_stride < p.gens) || (p.settled && !p.prev) || (clipped && (p.vis_w < 1 || p.vis_h < 1)))
         return hipErrorInvalidValue;
     const int64_t waves = batch_lanes(p.height, p.boards).waves;
     const dim3 grid((unsigned)((waves + kWavesPerWG - 1) / kWavesPerWG));
+    if (rules)
+        return clipped ? launch_step_flags<false, true, true>(p, grid, stream)
+                       : launch_step_flags<false, false, true>(p, grid, stream);
     if (life) return clipped ? launch_step_flags<true, true>(p, grid, stream) : launch_step_flags<true, false>(p, grid, stream);
     return clipped ? launch_step_flags<false, true>(p, grid, stream) : launch_step_flags<false, false>(p, grid, stream);
 }
 
-hipError_t launch_batch_cycle(const CycleParams& p, bool life, bool clipped, hipStream_t stream) {
-    // every index the kernel forms stays inside the two planes and the per-board words
-    if (!p.plane || !p.snap || !p.period || !p.seen || !p.counters || p.boards < 1 || p.boards > kMaxBoards ||
+hipError_t launch_batch_cycle(const CycleParams& p, bool life, bool clipped, bool rules, hipStream_t stream) {
+    // every index the kernel forms stays inside the two planes, the per-board words and the rule words
+    if (rules != (p.rules != nullptr) ||
+        !p.plane || !p.snap || !p.period || !p.seen || !p.counters || p.boards < 1 || p.boards > kMaxBoards ||
         p.width < 1 || p.width > kLanes || p.height < 1 || p.height > kLanes ||
         p.boards_per_wave != batch_lanes(p.height, p.boards).boards_per_wave || p.gens < 1 ||
         p.gens > UINT32_MAX - p.g0 ||
@@ -319,6 +372,9 @@ hipError_t launch_batch_cycle(const CycleParams& p, bool life, bool clipped, hip
         return hipErrorInvalidValue;
     const int64_t waves = batch_lanes(p.height, p.boards).waves;
     const dim3 grid((unsigned)((waves + kWavesPerWG - 1) / kWavesPerWG)), block(kLanes * kWavesPerWG);
+    if (rules)
+        return clipped ? gol::launch_kernel(batch_cycle_kernel<false, true, true>, grid, block, stream, p)
+                       : gol::launch_kernel(batch_cycle_kernel<false, false, true>, grid, block, stream, p);
     if (life)
         return clipped ? gol::launch_kernel(batch_cycle_kernel<true, true>, grid, block, stream, p)
                        : gol::launch_kernel(batch_cycle_kernel<true, false>, grid, block, stream, p);

@@ -186,6 +186,9 @@ GOL_CENSUS_BATCH_MAX_KEYS = 1 << 20
 GOL_FIND_BATCH_MAX_PATTERNS = 256
 GOL_FIND_BATCH_AUTO_CUT = 2048
 
+# gol_rules_batch_*: the bits a rule word may have set -- GOL_BATCH_RULE(birth, survive) (include/gol.h)
+GOL_BATCH_RULE_BITS = 0x01FF01FF
+
 # gol_write_region modes (include/gol.h GOL_REGION_*)
 GOL_REGION_COPY = 0
 GOL_REGION_OR = 1
@@ -295,6 +298,9 @@ _SIGNATURES = {
     "gol_census_batch_read": (_c.c_int, [_vp, ctypes.POINTER(GolCensusEntry), _c.c_size_t,
                                          ctypes.POINTER(_c.c_size_t)]),
     "gol_census_batch_stats": (_c.c_int, [_vp, _u64p, _u64p, _u64p, _u64p, _u64p, _u64p]),
+    "gol_rules_batch_check": (_c.c_int, [ctypes.POINTER(GolBatchConfig), _c.c_int64, _c.c_int64, _u32p]),
+    "gol_rules_batch_set": (_c.c_int, [_vp, _c.c_int64, _c.c_int64, _u32p]),
+    "gol_rules_batch_get": (_c.c_int, [_vp, _c.c_int64, _c.c_int64, _u32p]),
 }
 
 

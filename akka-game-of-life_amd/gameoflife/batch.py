@@ -2,8 +2,8 @@
 
 Where the reference runs one BoardCreator -- one actor system -- per board
 (BoardCreator.scala:18-23), a ``GolBatch`` holds ``boards`` boards of one
-geometry and rule, each at most 64 x 64 stored cells, and advances all of
-them per launch through libgol's gol_batch_* entry points: random soups until
+geometry, each at most 64 x 64 stored cells, under one rule or a rule per
+board (set_rules: a rule sweep), and advances all of them per launch through libgol's gol_batch_* entry points: random soups until
 they settle, one pattern under many perturbations, or many copies of the
 reference's own 7 x 7 board.  A board's row is one uint64 (bit x = cell x).
 """
@@ -15,7 +15,7 @@ import numpy as np
 
 from . import _native as N
 from . import patterns as P
-from .rules import Rule, rule_by_name
+from .rules import Rule, rule_by_name, rule_word
 
 # gol_batch_object as a numpy record (N.GolBatchObject's fields in its order, 16 bytes)
 OBJECT_DTYPE = P.OBJECT_DTYPE
@@ -286,6 +286,35 @@ class GolBatch:
         self._chk(N.lib.gol_census_batch_stats(self._h, *[ctypes.byref(x) for x in v]))
         return dict(zip(("calls", "seen", "tallied", "truncated", "overflowed", "distinct"), (x.value for x in v)))
 
+    def set_rules(self, rules, first: int = 0) -> None:
+        """Boards first .. first + n - 1 take rules of their own
+        (gol_rules_batch_set), and from then on step and step_cycles advance
+        board i under rule i, exactly as a batch created with that rule
+        would.  `rules` is a uint32 array of rule words (rules.rule_word,
+        rule_sweep_words) or a sequence of Rule, names or notations
+        ("B36/S23") or (birth, survive) pairs; the boards never named keep
+        the batch's rule.  None: every board back to the batch's rule.
+        Changes neither the boards nor the epoch."""
+        if rules is None:
+            self._chk(N.lib.gol_rules_batch_set(self._h, 0, self.boards, None))
+            return
+        if isinstance(rules, np.ndarray) and rules.dtype.kind in "ui":
+            if rules.size and (int(rules.min()) < 0 or int(rules.max()) > 0xFFFFFFFF):
+                raise ValueError("rule words are uint32")
+            words = np.ascontiguousarray(rules, dtype=np.uint32).reshape(-1)
+        else:
+            words = np.array([rule_word(r) for r in rules], dtype=np.uint32)
+        self._chk(N.lib.gol_rules_batch_set(self._h, first, words.size, words.ctypes.data_as(N._u32p)))
+
+    def rules(self, first: int = 0, count: int | None = None) -> np.ndarray:
+        """uint32 [n]: the rule words in force for boards first .. first +
+        count - 1 (rules.rule_from_word turns one into a Rule) -- the batch's
+        own rule where none was set."""
+        count = self.boards - first if count is None else count
+        out = np.zeros(max(count, 0), dtype=np.uint32)
+        self._chk(N.lib.gol_rules_batch_get(self._h, first, count, out.ctypes.data_as(N._u32p)))
+        return out
+
     @property
     def epoch(self) -> int:
         e = ctypes.c_uint64(0)
@@ -295,6 +324,18 @@ class GolBatch:
     def set_chunk(self, n: int) -> None:
         """Generations per launch (0: automatic); results never depend on it."""
         self._chk(N.lib.gol_batch_set_chunk(self._h, n))
+
+
+def rule_sweep_words(births, survives) -> np.ndarray:
+    """uint32 [len(births) * len(survives)]: the rule words (rules.rule_word)
+    of the cross product of two lists of 9-bit masks, births outermost --
+    word [i * len(survives) + j] is (births[i], survives[j]).
+    rule_sweep_words(range(512), range(512)) is every Life-like rule."""
+    b = np.asarray(list(births), dtype=np.int64).reshape(-1)
+    s = np.asarray(list(survives), dtype=np.int64).reshape(-1)
+    if (b & ~0x1FF).any() or (s & ~0x1FF).any():
+        raise ValueError("rule masks must fit in 9 bits")
+    return (b[:, None] | (s[None, :] << 16)).astype(np.uint32).reshape(-1)
 
 
 def tally(counts, objects, table) -> dict:

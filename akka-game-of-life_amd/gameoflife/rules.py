@@ -38,6 +38,31 @@ REF_EFFECTIVE = Rule(0x000, 0x1FF, "ref-effective")
 NAMED = {r.name: r for r in (LIFE, REF_LITERAL, REF_EFFECTIVE)}
 
 
+def rule_word(rule) -> int:
+    """The rule word of a batch's per-board rules (GOL_BATCH_RULE of
+    include/gol.h): birth in bits 0..8, survive in bits 16..24.  `rule` is a
+    Rule, a name or notation, or a (birth, survive) pair."""
+    if isinstance(rule, str):
+        rule = rule_by_name(rule)
+    birth, survive = (rule.birth, rule.survive) if isinstance(rule, Rule) else rule
+    birth, survive = int(birth), int(survive)
+    if (birth | survive) & ~0x1FF:
+        raise ValueError(f"rule masks must fit in 9 bits, not ({birth:#x}, {survive:#x})")
+    return birth | (survive << 16)
+
+
+def rule_from_word(word: int) -> Rule:
+    """The Rule a rule word stands for, under its name if it has one."""
+    word = int(word)
+    if word & ~0x01FF01FF:
+        raise ValueError(f"{word:#010x} is no rule word: bits 0..8 are the birth mask, bits 16..24 the survive mask")
+    rule = Rule(word & 0x1FF, (word >> 16) & 0x1FF)
+    for named in NAMED.values():
+        if (named.birth, named.survive) == (rule.birth, rule.survive):
+            return named
+    return Rule(rule.birth, rule.survive, rule.notation())
+
+
 def rule_by_name(name: str) -> Rule:
     """'life' | 'ref-literal' | 'ref-effective' | 'B3/S23'-style notation."""
     if name in NAMED:

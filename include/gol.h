@@ -66,7 +66,8 @@ extern "C" {
  * objects (gol_objects_batch_check, gol_objects_batch,
  * gol_objects_batch_stats) and its census (gol_census_batch_check,
  * gol_census_batch_begin, gol_census_batch_add, gol_census_batch_add_records,
- * gol_census_batch_read, gol_census_batch_stats). */
+ * gol_census_batch_read, gol_census_batch_stats) and its per-board rules
+ * (gol_rules_batch_check, gol_rules_batch_set, gol_rules_batch_get). */
 #define GOL_ABI_VERSION 2
 
 /* Return codes. */
@@ -854,6 +855,46 @@ int gol_census_batch_add_records(gol_batch* batch, const gol_batch_object* recor
 int gol_census_batch_read(gol_batch* batch, gol_census_entry* entries_out, size_t capacity, size_t* n_out);
 int gol_census_batch_stats(gol_batch* batch, uint64_t* calls, uint64_t* seen, uint64_t* tallied,
                            uint64_t* truncated, uint64_t* overflowed, uint64_t* distinct);
+
+/* Per-board rules: a rule sweep in one launch -- one
+ * soup, or one soup per rule, under as many rules as the batch has boards.  A
+ * batch is created with one rule, its configuration's; gol_rules_batch_set
+ * gives boards [first, first + count) rules of their own, and from then on
+ * gol_batch_step and gol_cycle_step advance board i under rule i: bit for bit
+ * what board i of a batch created with rule i and holding the same cells
+ * does -- the boards after any number of generations, populations_out,
+ * settled_out, period_out, seen_out and the epoch, whatever
+ * gol_batch_set_chunk says.  Everything that looks at cells only
+ * (gol_batch_hashes, gol_find_batch, gol_objects_batch, gol_census_batch_*)
+ * works on such a batch unchanged.  As with gol_cycle_* the names are not
+ * gol_batch_*: the handle is the batch, the capability its own.
+ *
+ * A rule is one uint32_t word per board: the birth mask in bits 0..8 and the
+ * survive mask in bits 16..24, GOL_BATCH_RULE(birth, survive); a word with any
+ * other bit set is refused.
+ *
+ * gol_rules_batch_set: boards first .. first + count - 1 take rules[0 ..
+ * count - 1]; the boards never named keep the configuration's rule.  It
+ * changes neither the boards nor the epoch.  rules == NULL with first == 0 and
+ * count == boards returns the batch to its configuration's rule and to the
+ * kernels a batch without per-board rules runs (rules == NULL with any other
+ * range is refused).  GOL_EINVAL, with nothing changed and the index of the
+ * offending word in the message, for a bad word; GOL_EINVAL, with nothing
+ * changed, for a range outside the batch or a NULL handle.  The first call
+ * allocates the device's [boards] words (GOL_ENOMEM, and nothing changed, if
+ * it cannot); gol_batch_destroy frees them, and gol_batch_geometry_get's
+ * device_bytes stays what gol_batch_create allocates, as for the cycle words
+ * and the census.  Synchronises.
+ *
+ * gol_rules_batch_get: the rules in force for boards [first, first + count),
+ * the configuration's word where none was set.  Needs no device work.
+ *
+ * gol_rules_batch_check validates first, count and rules for a geometry as
+ * gol_rules_batch_set does, and needs no device. */
+#define GOL_BATCH_RULE(birth, survive) ((uint32_t)(((uint32_t)(birth) & 0x1FFu) | (((uint32_t)(survive) & 0x1FFu) << 16)))
+int gol_rules_batch_check(const gol_batch_config* cfg, int64_t first, int64_t count, const uint32_t* rules);
+int gol_rules_batch_set(gol_batch* batch, int64_t first, int64_t count, const uint32_t* rules);
+int gol_rules_batch_get(gol_batch* batch, int64_t first, int64_t count, uint32_t* rules_out);
 
 /* Kernel timing: when enabled, the dominant step-kernel launch of every pass
  * (the whole shard, or a sharded shard's interior rows) is bracketed by HIP
