@@ -6,7 +6,9 @@
 // and those tallied by one (gol_batch_census.hip).  A
 // handle type of its own: it shares the error conventions and the HIP status
 // discipline with the contexts (gol_ctx.h), and nothing else -- no planner, no
-// step kernel.
+// step kernel.  Every device buffer of the handle has one owner (DevBuf), the
+// handle's fields are grouped by the calls they serve, and a refusal that more
+// than one entry point gives is formatted in one place.
 #include <algorithm>
 #include <cstdarg>
 #include <cstdio>
@@ -16,6 +18,50 @@
 #include "gol_batch.h"
 #include "gol_ctx.h"
 
+namespace {
+
+using golc::hip_note;
+
+// A device buffer of the handle and its owner (golc::Accum's idiom, as small
+// as the batch needs): the pointer and how many elements it holds.  Whoever
+// destroys it has set the device and synchronised the stream.
+template <class T>
+struct DevBuf {
+    T* dev = nullptr;
+    size_t count = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { release("batch destroy: hipFree"); }
+    // Forgets the buffer before freeing it; a failing hipFree is noted under the caller's label.
+    void release(const char* label) {
+        T* const d = dev;
+        dev = nullptr;
+        count = 0;
+        if (d) hip_note(hipFree(d), label);
+    }
+    // Holds at least n elements afterwards.  A buffer that is too small is replaced (nothing is in flight on it:
+    // every call synchronises); false, with nothing held and the HIP status taken off the thread, if it cannot be.
+    bool grow(size_t n, const char* label) {
+        if (n <= count) return true;
+        release(label);
+        void* p = nullptr;
+        if (hipMalloc(&p, n * sizeof(T)) != hipSuccess) {
+            (void)hipGetLastError();
+            return false;
+        }
+        dev = static_cast<T*>(p);
+        count = n;
+        return true;
+    }
+    void swap(DevBuf& o) {
+        std::swap(dev, o.dev);
+        std::swap(count, o.count);
+    }
+};
+
+}  // namespace
+
 struct gol_batch {
     golbatch::Geometry geo{};
     golbatch::Lanes lanes{};
@@ -24,61 +70,61 @@ struct gol_batch {
     uint32_t chunk = 0;  // gol_batch_set_chunk (0: automatic)
     uint64_t epoch = 0;
     hipStream_t stream = nullptr;
-    unsigned long long* plane = nullptr;  // boards * height rows
+    DevBuf<unsigned long long> plane;  // boards * height rows
     // the plane one generation before (settle detection across launches), or a cycle call's snapshot plane: a call
     // is one or the other, and neither reads what an earlier call left in it
-    unsigned long long* prev = nullptr;
-    uint32_t* settled = nullptr;          // [boards]
+    DevBuf<unsigned long long> prev;
+    DevBuf<uint32_t> settled;  // [boards]
+    DevBuf<uint32_t> series;   // the series of one launch, [boards][count / boards], grown on demand
     // gol_cycle_step's words, allocated by its first call: period [boards], seen [boards], then the two counters
-    // (boards that have a period, the largest period)
-    uint32_t* cycle_words = nullptr;
-    uint64_t cycle_launches = 0, cycle_boards = 0;  // gol_cycle_stats: the last gol_cycle_step call
-    uint32_t cycle_max_period = 0;
-    // the series of one launch, [boards][series_gens] (grown on demand), and gol_batch_hashes' results
-    uint32_t* series = nullptr;
-    size_t series_gens = 0;
-    unsigned long long* hashes = nullptr;
-    uint32_t* hash_pops = nullptr;
-    size_t hashes_count = 0;
+    // (boards that have a period, the largest period); gol_cycle_stats: the last gol_cycle_step call
+    struct {
+        DevBuf<uint32_t> words;
+        uint64_t launches = 0, boards = 0;
+        uint32_t max_period = 0;
+    } cycle;
+    // gol_batch_hashes' results, grown on demand and together
+    struct {
+        DevBuf<unsigned long long> values;
+        DevBuf<uint32_t> pops;
+    } hashes;
     // gol_find_batch's buffers, grown on demand: the pattern table (headers, then the row pairs), the counts
     // [boards][npatterns] and the match planes [npatterns][boards][height]
-    void* find_table = nullptr;
-    size_t find_table_bytes = 0;
-    uint32_t* find_counts = nullptr;
-    size_t find_counts_n = 0;
-    unsigned long long* find_matches = nullptr;
-    size_t find_matches_n = 0;
-    uint32_t find_cut = 0;  // gol_find_batch_set_cut (0: automatic)
-    uint64_t find_launches = 0, find_cared = 0;  // gol_find_batch_stats: the last gol_find_batch call
+    struct {
+        DevBuf<unsigned char> table;
+        DevBuf<uint32_t> counts;
+        DevBuf<unsigned long long> matches;
+        uint32_t cut = 0;                  // gol_find_batch_set_cut (0: automatic)
+        uint64_t launches = 0, cared = 0;  // gol_find_batch_stats: the last gol_find_batch call
+    } find;
     // gol_objects_batch's buffers, grown on demand: the counts [count] and the records [count][max_objects]
-    uint32_t* obj_counts = nullptr;
-    size_t obj_counts_n = 0;
-    gol_batch_object* obj_records = nullptr;
-    size_t obj_records_n = 0;
-    // gol_objects_batch_stats: the last gol_objects_batch call
-    uint64_t obj_launches = 0, obj_total = 0, obj_truncated = 0;
-    // gol_census_batch_*'s table (census_capacity slots, 0: no census has begun) and counters, the calls since
+    struct {
+        DevBuf<uint32_t> counts;
+        DevBuf<gol_batch_object> records;
+        uint64_t launches = 0, total = 0, truncated = 0;  // gol_objects_batch_stats: the last gol_objects_batch call
+    } objects;
+    // gol_census_batch_*'s table (four qwords a slot; none: no census has begun) and counters, the calls since
     // begin, and the buffers, grown on demand, add_records' records and read's entries pass through
-    unsigned long long* census_slots = nullptr;
-    unsigned long long* census_counters = nullptr;
-    uint32_t census_capacity = 0;
-    uint64_t census_calls = 0;
-    gol_batch_object* census_in = nullptr;
-    size_t census_in_n = 0;
-    gol_census_entry* census_out = nullptr;
-    size_t census_out_n = 0;
+    struct {
+        DevBuf<unsigned long long> slots, counters;
+        uint64_t calls = 0;
+        DevBuf<gol_batch_object> in;
+        DevBuf<gol_census_entry> out;
+        uint32_t capacity() const { return (uint32_t)(slots.count / 4); }
+        golbatch::CensusTable table() const { return {slots.dev, counters.dev, capacity()}; }
+    } census;
     // gol_rules_batch_*: the device's rule words [boards], allocated by the first set; their host copy, the rules
     // in force (empty before the first set: the configuration's rule everywhere); and whether the steps launch the
     // RULES instances
-    uint32_t* rules = nullptr;
-    std::vector<uint32_t> rules_host;
-    bool rules_on = false;
+    struct {
+        DevBuf<uint32_t> words;
+        std::vector<uint32_t> host;
+        bool on = false;
+    } rules;
     std::string err;
 };
 
 namespace {
-
-using golc::hip_note;
 
 int batch_err(gol_batch* b, int code, const char* fmt, ...) {
     char buf[512];
@@ -112,39 +158,47 @@ bool life_rule(const gol_batch* b) {
 
 size_t plane_words(const gol_batch* b) { return (size_t)b->geo.boards * (size_t)b->geo.height; }
 
-// boards [first, first + count) inside the batch
-bool window_ok(const gol_batch* b, int64_t first, int64_t count) {
-    return first >= 0 && count >= 1 && first < b->geo.boards && count <= (int64_t)b->geo.boards - first;
-}
-
+// The buffers release themselves with the handle, after the stream has drained and before it goes.
 void destroy_impl(gol_batch* b) {
     hip_note(hipSetDevice(b->device), "batch destroy: hipSetDevice");
-    if (b->stream) hip_note(hipStreamSynchronize(b->stream), "batch destroy: hipStreamSynchronize");
-    for (void* p : {(void*)b->plane, (void*)b->prev, (void*)b->settled, (void*)b->series, (void*)b->hashes,
-                    (void*)b->hash_pops, (void*)b->cycle_words, b->find_table, (void*)b->find_counts,
-                    (void*)b->find_matches, (void*)b->obj_counts, (void*)b->obj_records, (void*)b->census_slots,
-                    (void*)b->census_counters, (void*)b->census_in, (void*)b->census_out, (void*)b->rules})
-        if (p) hip_note(hipFree(p), "batch destroy: hipFree");
-    if (b->stream) hip_note(hipStreamDestroy(b->stream), "batch destroy: hipStreamDestroy");
+    const hipStream_t stream = b->stream;
+    if (stream) hip_note(hipStreamSynchronize(stream), "batch destroy: hipStreamSynchronize");
     delete b;
+    if (stream) hip_note(hipStreamDestroy(stream), "batch destroy: hipStreamDestroy");
 }
 
-// A buffer of the handle that holds at least `want` elements of `elem` bytes (nothing is in flight on the old one:
-// every call synchronises).  False, with the buffer gone, if it cannot be had.
-template <class T>
-bool grow(T*& buf, size_t& have, size_t want, size_t elem) {
-    if (have >= want) return true;
-    if (buf) hip_note(hipFree(buf), "gol_find_batch: hipFree");
-    buf = nullptr;
-    have = 0;
-    void* p = nullptr;
-    if (hipMalloc(&p, want * elem) != hipSuccess) {
-        (void)hipGetLastError();
-        return false;
-    }
-    buf = static_cast<T*>(p);
-    have = want;
-    return true;
+// The geometry of a configuration, or its refusal as a message
+int config_geometry(const gol_batch_config* cfg, golbatch::Geometry* g) {
+    if (const char* why = golbatch::batch_geometry(*cfg, g))
+        return batch_err(nullptr, GOL_EINVAL, "batch of %d boards %d x %d: %s", cfg->boards, cfg->width, cfg->height,
+                         why);
+    return GOL_OK;
+}
+
+// window_ok's refusal as a message
+int window_refusal(gol_batch* b, const char* fn, int64_t first, int64_t count) {
+    return batch_err(b, GOL_EINVAL, "%s: boards [%lld, %lld + %lld) outside the batch of %d", fn, (long long)first,
+                     (long long)first, (long long)count, b->geo.boards);
+}
+
+// A launch's parameters with what they take from the handle's geometry: boards, width, height, boards_per_wave
+// and, where P has them, vis_w and vis_h
+template <class P>
+auto set_visible(P& p, const golbatch::Geometry& g, int) -> decltype((void)p.vis_w) {
+    p.vis_w = g.vis_w;
+    p.vis_h = g.vis_h;
+}
+template <class P>
+void set_visible(P&, const golbatch::Geometry&, long) {}
+template <class P>
+P launch_params(const gol_batch* b) {
+    P p{};
+    p.boards = b->geo.boards;
+    p.width = b->geo.width;
+    p.height = b->geo.height;
+    p.boards_per_wave = b->lanes.boards_per_wave;
+    set_visible(p, b->geo, 0);
+    return p;
 }
 
 // "pattern 3: ..." or "...": batch_find_patterns' refusal as a message
@@ -158,22 +212,17 @@ int find_refusal(gol_batch* b, const char* fn, const char* why, int32_t which) {
 int launch_objects(gol_batch* batch, const char* fn, int64_t first, int64_t count, int32_t reach,
                    int32_t max_objects) {
     const size_t n = (size_t)count, records_n = n * (size_t)max_objects;  // <= 2^22 * 2^10
-    if (!grow(batch->obj_counts, batch->obj_counts_n, n, sizeof(uint32_t)) ||
-        !grow(batch->obj_records, batch->obj_records_n, records_n, sizeof(gol_batch_object)))
+    if (!batch->objects.counts.grow(n, "gol_objects_batch: hipFree") ||
+        !batch->objects.records.grow(records_n, "gol_objects_batch: hipFree"))
         return batch_err(batch, GOL_ENOMEM, "%s: hipMalloc of the counts (%zu entries) or the records "
                          "(%zu entries) failed; nothing written", fn, n, records_n);
     // the records past a board's count are zero: one memset before the launch, the kernel stores the real ones only
-    BATCH_HIP(batch, hipMemsetAsync(batch->obj_records, 0, records_n * sizeof(gol_batch_object), batch->stream));
-    golbatch::ObjectsParams p{};
-    p.plane = batch->plane;
-    p.counts = batch->obj_counts;
-    p.objects = reinterpret_cast<uint4*>(batch->obj_records);
-    p.boards = (int32_t)(first + count);
-    p.width = batch->geo.width;
-    p.height = batch->geo.height;
-    p.boards_per_wave = batch->lanes.boards_per_wave;
-    p.vis_w = batch->geo.vis_w;
-    p.vis_h = batch->geo.vis_h;
+    BATCH_HIP(batch, hipMemsetAsync(batch->objects.records.dev, 0, records_n * sizeof(gol_batch_object), batch->stream));
+    auto p = launch_params<golbatch::ObjectsParams>(batch);
+    p.plane = batch->plane.dev;
+    p.counts = batch->objects.counts.dev;
+    p.objects = reinterpret_cast<uint4*>(batch->objects.records.dev);
+    p.boards = (int32_t)(first + count);  // the end of the range
     p.first = (int32_t)first;
     p.reach = reach;
     p.max_objects = max_objects;
@@ -191,15 +240,20 @@ int rules_refusal(gol_batch* b, const char* fn, const char* why, const golbatch:
                      (long long)count, g.boards);
 }
 
-golbatch::CensusTable census_table(const gol_batch* b) {
-    return {b->census_slots, b->census_counters, b->census_capacity};
-}
-
 // batch_census_args for a call of this handle: the request's handle fields filled in
 const char* census_refusal(const gol_batch* b, golbatch::CensusRequest r) {
-    r.begun = b->census_capacity != 0;
-    r.next_call = b->census_calls;
+    r.begun = b->census.capacity() != 0;
+    r.next_call = b->census.calls;
     return golbatch::batch_census_args(b->geo, r);
+}
+
+// The census's counters as the device has them now
+int census_counters(gol_batch* batch, unsigned long long (&counters)[golbatch::kCensusCounters]) {
+    BATCH_HIP(batch, hipSetDevice(batch->device));
+    BATCH_HIP(batch, hipMemcpyAsync(counters, batch->census.counters.dev, sizeof counters, hipMemcpyDeviceToHost,
+                                    batch->stream));
+    BATCH_HIP(batch, hipStreamSynchronize(batch->stream));
+    return GOL_OK;
 }
 
 }  // namespace
@@ -209,9 +263,7 @@ extern "C" {
 int gol_batch_geometry_get(const gol_batch_config* cfg, gol_batch_geometry* out) {
     if (!cfg || !out) return batch_err(nullptr, GOL_EINVAL, "gol_batch_geometry_get: null argument");
     golbatch::Geometry g;
-    if (const char* why = golbatch::batch_geometry(*cfg, &g))
-        return batch_err(nullptr, GOL_EINVAL, "batch of %d boards %d x %d: %s", cfg->boards, cfg->width, cfg->height,
-                         why);
+    if (const int rc = config_geometry(cfg, &g)) return rc;
     const golbatch::Lanes l = golbatch::batch_lanes(g.height, g.boards);
     out->boards_per_wave = l.boards_per_wave;
     out->waves = l.waves;
@@ -223,9 +275,7 @@ int gol_batch_create(gol_batch** out, const gol_batch_config* cfg) {
     if (!out || !cfg) return batch_err(nullptr, GOL_EINVAL, "gol_batch_create: null argument");
     *out = nullptr;
     golbatch::Geometry g;
-    if (const char* why = golbatch::batch_geometry(*cfg, &g))
-        return batch_err(nullptr, GOL_EINVAL, "batch of %d boards %d x %d: %s", cfg->boards, cfg->width, cfg->height,
-                         why);
+    if (const int rc = config_geometry(cfg, &g)) return rc;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
         (void)hipGetLastError();
@@ -248,11 +298,12 @@ int gol_batch_create(gol_batch** out, const gol_batch_config* cfg) {
     if (hipSetDevice(b->device) != hipSuccess) return fail(GOL_EHIP, "hipSetDevice");
     const size_t bytes = plane_words(b) * sizeof(unsigned long long);
     const size_t settle_bytes = (size_t)g.boards * sizeof(uint32_t);
-    if (hipMalloc(&b->plane, bytes) != hipSuccess || hipMalloc(&b->prev, bytes) != hipSuccess ||
-        hipMalloc(&b->settled, settle_bytes) != hipSuccess)
+    const char* const label = "gol_batch_create: hipFree";
+    if (!b->plane.grow(plane_words(b), label) || !b->prev.grow(plane_words(b), label) ||
+        !b->settled.grow((size_t)g.boards, label))
         return fail(GOL_ENOMEM, "hipMalloc of the planes");
-    if (hipMemset(b->plane, 0, bytes) != hipSuccess || hipMemset(b->prev, 0, bytes) != hipSuccess ||
-        hipMemset(b->settled, 0, settle_bytes) != hipSuccess)
+    if (hipMemset(b->plane.dev, 0, bytes) != hipSuccess || hipMemset(b->prev.dev, 0, bytes) != hipSuccess ||
+        hipMemset(b->settled.dev, 0, settle_bytes) != hipSuccess)
         return fail(GOL_EHIP, "hipMemset");
     if (hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking) != hipSuccess)
         return fail(GOL_EHIP, "hipStreamCreateWithFlags");
@@ -272,7 +323,7 @@ const char* gol_batch_last_error(const gol_batch* batch) {
 int gol_batch_seed(gol_batch* batch, uint64_t seed) {
     if (!batch) return batch_err(nullptr, GOL_EINVAL, "gol_batch_seed: null handle");
     BATCH_HIP(batch, hipSetDevice(batch->device));
-    BATCH_HIP(batch, golbatch::launch_batch_seed(batch->plane, (int64_t)plane_words(batch), batch->geo.width, seed,
+    BATCH_HIP(batch, golbatch::launch_batch_seed(batch->plane.dev, (int64_t)plane_words(batch), batch->geo.width, seed,
                                                  batch->stream));
     BATCH_HIP(batch, hipStreamSynchronize(batch->stream));
     batch->epoch = 0;
@@ -282,15 +333,13 @@ int gol_batch_seed(gol_batch* batch, uint64_t seed) {
 int gol_batch_load(gol_batch* batch, int64_t first, int64_t count, const uint64_t* rows) {
     if (!batch) return batch_err(nullptr, GOL_EINVAL, "gol_batch_load: null handle");
     if (!rows) return batch_err(batch, GOL_EINVAL, "gol_batch_load: rows is null");
-    if (!window_ok(batch, first, count))
-        return batch_err(batch, GOL_EINVAL, "gol_batch_load: boards [%lld, %lld + %lld) outside the batch of %d",
-                         (long long)first, (long long)first, (long long)count, batch->geo.boards);
+    if (!golbatch::window_ok(batch->geo, first, count)) return window_refusal(batch, "gol_batch_load", first, count);
     const size_t H = (size_t)batch->geo.height, n = (size_t)count * H;
     const uint64_t wmask = batch->geo.width >= 64 ? ~0ull : (1ull << batch->geo.width) - 1ull;
     std::vector<uint64_t> masked(n);  // bits at x >= width are ignored
     for (size_t i = 0; i < n; ++i) masked[i] = rows[i] & wmask;
     BATCH_HIP(batch, hipSetDevice(batch->device));
-    BATCH_HIP(batch, hipMemcpyAsync(batch->plane + (size_t)first * H, masked.data(), n * sizeof(uint64_t),
+    BATCH_HIP(batch, hipMemcpyAsync(batch->plane.dev + (size_t)first * H, masked.data(), n * sizeof(uint64_t),
                                     hipMemcpyHostToDevice, batch->stream));
     BATCH_HIP(batch, hipStreamSynchronize(batch->stream));
     batch->epoch = 0;
@@ -300,13 +349,11 @@ int gol_batch_load(gol_batch* batch, int64_t first, int64_t count, const uint64_
 int gol_batch_snapshot(gol_batch* batch, int64_t first, int64_t count, uint64_t* rows) {
     if (!batch) return batch_err(nullptr, GOL_EINVAL, "gol_batch_snapshot: null handle");
     if (!rows) return batch_err(batch, GOL_EINVAL, "gol_batch_snapshot: rows is null");
-    if (!window_ok(batch, first, count))
-        return batch_err(batch, GOL_EINVAL, "gol_batch_snapshot: boards [%lld, %lld + %lld) outside the batch of %d",
-                         (long long)first, (long long)first, (long long)count, batch->geo.boards);
+    if (!golbatch::window_ok(batch->geo, first, count)) return window_refusal(batch, "gol_batch_snapshot", first, count);
     const size_t H = (size_t)batch->geo.height;
     BATCH_HIP(batch, hipSetDevice(batch->device));
     // the plane never holds a bit at x >= width: every writer masks
-    BATCH_HIP(batch, hipMemcpyAsync(rows, batch->plane + (size_t)first * H, (size_t)count * H * sizeof(uint64_t),
+    BATCH_HIP(batch, hipMemcpyAsync(rows, batch->plane.dev + (size_t)first * H, (size_t)count * H * sizeof(uint64_t),
                                     hipMemcpyDeviceToHost, batch->stream));
     BATCH_HIP(batch, hipStreamSynchronize(batch->stream));
     return GOL_OK;
@@ -322,48 +369,32 @@ int gol_batch_step(gol_batch* batch, uint32_t generations, uint32_t* populations
     if (generations == 0) return GOL_OK;
     const uint32_t chunk = std::min(batch->chunk ? batch->chunk : golbatch::kAutoChunk, generations);
     BATCH_HIP(batch, hipSetDevice(batch->device));
-    if (populations_out && batch->series_gens < chunk) {
-        // nothing is in flight on the old buffer: every call synchronises
-        if (batch->series) BATCH_HIP(batch, hipFree(batch->series));
-        batch->series = nullptr;
-        batch->series_gens = 0;
-        const size_t bytes = boards * (size_t)chunk * sizeof(uint32_t);
-        if (hipMalloc(&batch->series, bytes) != hipSuccess) {
-            (void)hipGetLastError();
-            batch->series = nullptr;
-            return batch_err(batch, GOL_ENOMEM, "gol_batch_step: hipMalloc of %zu bytes for the population series "
-                             "failed; nothing advanced", bytes);
-        }
-        batch->series_gens = chunk;
-    }
-    golbatch::StepParams p{};
-    p.plane = batch->plane;
-    p.prev = batch->prev;
-    p.pops = populations_out ? batch->series : nullptr;
-    p.settled = settled_out ? batch->settled : nullptr;
-    p.boards = batch->geo.boards;
-    p.width = batch->geo.width;
-    p.height = batch->geo.height;
-    p.boards_per_wave = batch->lanes.boards_per_wave;
-    p.vis_w = batch->geo.vis_w;
-    p.vis_h = batch->geo.vis_h;
-    p.pop_stride = (uint32_t)batch->series_gens;
+    if (populations_out && !batch->series.grow(boards * (size_t)chunk, "gol_batch_step: hipFree"))
+        return batch_err(batch, GOL_ENOMEM, "gol_batch_step: hipMalloc of %zu bytes for the population series "
+                         "failed; nothing advanced", boards * (size_t)chunk * sizeof(uint32_t));
+    const size_t series_gens = batch->series.count / boards;  // >= chunk with populations_out
+    auto p = launch_params<golbatch::StepParams>(batch);
+    p.plane = batch->plane.dev;
+    p.prev = batch->prev.dev;
+    p.pops = populations_out ? batch->series.dev : nullptr;
+    p.settled = settled_out ? batch->settled.dev : nullptr;
+    p.pop_stride = (uint32_t)series_gens;
     p.birth = batch->birth;
     p.survive = batch->survive;
-    p.rules = batch->rules_on ? batch->rules : nullptr;
+    p.rules = batch->rules.on ? batch->rules.words.dev : nullptr;
     for (uint32_t g0 = 0; g0 < generations; g0 += chunk) {
         p.gens = std::min(chunk, generations - g0);
         p.g0 = g0;
-        BATCH_HIP(batch, golbatch::launch_batch_step(p, life_rule(batch), batch->geo.clipped, batch->rules_on,
+        BATCH_HIP(batch, golbatch::launch_batch_step(p, life_rule(batch), batch->geo.clipped, batch->rules.on,
                                                      batch->stream));
         batch->epoch += p.gens;
         if (populations_out)  // this launch's columns of the caller's [boards][generations]; waits for the launch
-            BATCH_HIP(batch, hipMemcpy2DAsync(populations_out + g0, (size_t)generations * sizeof(uint32_t), batch->series,
-                                              batch->series_gens * sizeof(uint32_t), (size_t)p.gens * sizeof(uint32_t),
+            BATCH_HIP(batch, hipMemcpy2DAsync(populations_out + g0, (size_t)generations * sizeof(uint32_t),
+                                              batch->series.dev, series_gens * sizeof(uint32_t), (size_t)p.gens * sizeof(uint32_t),
                                               boards, hipMemcpyDeviceToHost, batch->stream));
     }
     if (settled_out)
-        BATCH_HIP(batch, hipMemcpyAsync(settled_out, batch->settled, boards * sizeof(uint32_t), hipMemcpyDeviceToHost,
+        BATCH_HIP(batch, hipMemcpyAsync(settled_out, batch->settled.dev, boards * sizeof(uint32_t), hipMemcpyDeviceToHost,
                                         batch->stream));
     BATCH_HIP(batch, hipStreamSynchronize(batch->stream));
     return GOL_OK;
@@ -383,33 +414,21 @@ int gol_cycle_step(gol_batch* batch, uint32_t generations, uint32_t* period_out,
     const size_t boards = (size_t)batch->geo.boards;
     const uint32_t chunk = batch->chunk ? batch->chunk : golbatch::kAutoChunk;
     BATCH_HIP(batch, hipSetDevice(batch->device));
-    if (!batch->cycle_words) {
-        const size_t bytes = (2 * boards + 2) * sizeof(uint32_t);
-        if (hipMalloc(&batch->cycle_words, bytes) != hipSuccess) {
-            (void)hipGetLastError();
-            batch->cycle_words = nullptr;
-            return batch_err(batch, GOL_ENOMEM, "gol_cycle_step: hipMalloc of %zu bytes for the period and seen words "
-                             "failed; nothing advanced", bytes);
-        }
-    }
-    golbatch::CycleParams p{};
-    p.plane = batch->plane;
-    p.snap = batch->prev;
-    p.period = batch->cycle_words;
-    p.seen = batch->cycle_words + boards;
-    p.counters = batch->cycle_words + 2 * boards;
-    p.boards = batch->geo.boards;
-    p.width = batch->geo.width;
-    p.height = batch->geo.height;
-    p.boards_per_wave = batch->lanes.boards_per_wave;
-    p.vis_w = batch->geo.vis_w;
-    p.vis_h = batch->geo.vis_h;
+    if (!batch->cycle.words.grow(2 * boards + 2, "gol_cycle_step: hipFree"))
+        return batch_err(batch, GOL_ENOMEM, "gol_cycle_step: hipMalloc of %zu bytes for the period and seen words "
+                         "failed; nothing advanced", (2 * boards + 2) * sizeof(uint32_t));
+    auto p = launch_params<golbatch::CycleParams>(batch);
+    p.plane = batch->plane.dev;
+    p.snap = batch->prev.dev;
+    p.period = batch->cycle.words.dev;
+    p.seen = batch->cycle.words.dev + boards;
+    p.counters = batch->cycle.words.dev + 2 * boards;
     p.birth = batch->birth;
     p.survive = batch->survive;
-    p.rules = batch->rules_on ? batch->rules : nullptr;
+    p.rules = batch->rules.on ? batch->rules.words.dev : nullptr;
     // the first launch of a call reads neither the words nor the snapshot plane; the counters start at zero
     BATCH_HIP(batch, hipMemsetAsync(p.counters, 0, 2 * sizeof(uint32_t), batch->stream));
-    batch->cycle_launches = 0;
+    batch->cycle.launches = 0;
     uint32_t counters[2] = {0u, 0u};
     for (uint32_t g0 = 0; g0 < generations; g0 += p.gens) {
         // every board cycled: a launch fast-forwards, at most max_period - 1 generations per board whatever it is
@@ -417,14 +436,14 @@ int gol_cycle_step(gol_batch* batch, uint32_t generations, uint32_t* period_out,
         const bool all = counters[0] == boards && counters[1] - 1u <= chunk;
         p.gens = all ? generations - g0 : std::min(chunk, generations - g0);
         p.g0 = g0;
-        BATCH_HIP(batch, golbatch::launch_batch_cycle(p, life_rule(batch), batch->geo.clipped, batch->rules_on,
+        BATCH_HIP(batch, golbatch::launch_batch_cycle(p, life_rule(batch), batch->geo.clipped, batch->rules.on,
                                                       batch->stream));
         batch->epoch += p.gens;
-        ++batch->cycle_launches;
+        ++batch->cycle.launches;
         BATCH_HIP(batch, hipMemcpyAsync(counters, p.counters, sizeof counters, hipMemcpyDeviceToHost, batch->stream));
         BATCH_HIP(batch, hipStreamSynchronize(batch->stream));
-        batch->cycle_boards = counters[0];
-        batch->cycle_max_period = counters[1];
+        batch->cycle.boards = counters[0];
+        batch->cycle.max_period = counters[1];
     }
     if (period_out)
         BATCH_HIP(batch, hipMemcpyAsync(period_out, p.period, boards * sizeof(uint32_t), hipMemcpyDeviceToHost,
@@ -438,9 +457,9 @@ int gol_cycle_step(gol_batch* batch, uint32_t generations, uint32_t* period_out,
 
 int gol_cycle_stats(gol_batch* batch, uint64_t* launches, uint64_t* boards_cycled, uint32_t* max_period) {
     if (!batch) return batch_err(nullptr, GOL_EINVAL, "gol_cycle_stats: null handle");
-    if (launches) *launches = batch->cycle_launches;
-    if (boards_cycled) *boards_cycled = batch->cycle_boards;
-    if (max_period) *max_period = batch->cycle_max_period;
+    if (launches) *launches = batch->cycle.launches;
+    if (boards_cycled) *boards_cycled = batch->cycle.boards;
+    if (max_period) *max_period = batch->cycle.max_period;
     return GOL_OK;
 }
 
@@ -448,35 +467,23 @@ int gol_batch_hashes(gol_batch* batch, int64_t first, int64_t count, uint64_t* h
                      uint32_t* populations_out) {
     if (!batch) return batch_err(nullptr, GOL_EINVAL, "gol_batch_hashes: null handle");
     if (!hashes_out && !populations_out) return batch_err(batch, GOL_EINVAL, "gol_batch_hashes: both arrays are null");
-    if (!window_ok(batch, first, count))
-        return batch_err(batch, GOL_EINVAL, "gol_batch_hashes: boards [%lld, %lld + %lld) outside the batch of %d",
-                         (long long)first, (long long)first, (long long)count, batch->geo.boards);
+    if (!golbatch::window_ok(batch->geo, first, count)) return window_refusal(batch, "gol_batch_hashes", first, count);
     BATCH_HIP(batch, hipSetDevice(batch->device));
     const size_t n = (size_t)count;
-    if (batch->hashes_count < n) {
-        if (batch->hashes) BATCH_HIP(batch, hipFree(batch->hashes));
-        batch->hashes = nullptr;
-        if (batch->hash_pops) BATCH_HIP(batch, hipFree(batch->hash_pops));
-        batch->hash_pops = nullptr;
-        batch->hashes_count = 0;
-        if (hipMalloc(&batch->hashes, n * sizeof(unsigned long long)) != hipSuccess ||
-            hipMalloc(&batch->hash_pops, n * sizeof(uint32_t)) != hipSuccess) {
-            (void)hipGetLastError();
-            if (batch->hashes) hip_note(hipFree(batch->hashes), "gol_batch_hashes: hipFree");
-            batch->hashes = nullptr;
-            batch->hash_pops = nullptr;
-            return batch_err(batch, GOL_ENOMEM, "gol_batch_hashes: hipMalloc for %zu boards failed", n);
-        }
-        batch->hashes_count = n;
+    const char* const label = "gol_batch_hashes: hipFree";
+    if (!batch->hashes.values.grow(n, label) || !batch->hashes.pops.grow(n, label)) {
+        batch->hashes.values.release(label);  // both or neither
+        batch->hashes.pops.release(label);
+        return batch_err(batch, GOL_ENOMEM, "gol_batch_hashes: hipMalloc for %zu boards failed", n);
     }
-    BATCH_HIP(batch, golbatch::launch_batch_hashes(batch->plane, batch->geo.height, first, count,
-                                                   hashes_out ? batch->hashes : nullptr,
-                                                   populations_out ? batch->hash_pops : nullptr, batch->stream));
+    BATCH_HIP(batch, golbatch::launch_batch_hashes(batch->plane.dev, batch->geo.height, first, count,
+                                                   hashes_out ? batch->hashes.values.dev : nullptr,
+                                                   populations_out ? batch->hashes.pops.dev : nullptr, batch->stream));
     if (hashes_out)
-        BATCH_HIP(batch, hipMemcpyAsync(hashes_out, batch->hashes, n * sizeof(uint64_t), hipMemcpyDeviceToHost,
+        BATCH_HIP(batch, hipMemcpyAsync(hashes_out, batch->hashes.values.dev, n * sizeof(uint64_t), hipMemcpyDeviceToHost,
                                         batch->stream));
     if (populations_out)
-        BATCH_HIP(batch, hipMemcpyAsync(populations_out, batch->hash_pops, n * sizeof(uint32_t), hipMemcpyDeviceToHost,
+        BATCH_HIP(batch, hipMemcpyAsync(populations_out, batch->hashes.pops.dev, n * sizeof(uint32_t), hipMemcpyDeviceToHost,
                                         batch->stream));
     BATCH_HIP(batch, hipStreamSynchronize(batch->stream));
     return GOL_OK;
@@ -485,9 +492,7 @@ int gol_batch_hashes(gol_batch* batch, int64_t first, int64_t count, uint64_t* h
 int gol_find_batch_check(const gol_batch_config* cfg, const gol_batch_pattern* patterns, int32_t npatterns) {
     if (!cfg) return batch_err(nullptr, GOL_EINVAL, "gol_find_batch_check: null configuration");
     golbatch::Geometry g;
-    if (const char* why = golbatch::batch_geometry(*cfg, &g))
-        return batch_err(nullptr, GOL_EINVAL, "batch of %d boards %d x %d: %s", cfg->boards, cfg->width, cfg->height,
-                         why);
+    if (const int rc = config_geometry(cfg, &g)) return rc;
     int32_t which = -1;
     if (const char* why = golbatch::batch_find_patterns(g, patterns, npatterns, &which))
         return find_refusal(nullptr, "gol_find_batch_check", why, which);
@@ -536,30 +541,25 @@ int gol_find_batch(gol_batch* batch, const gol_batch_pattern* patterns, int32_t 
     }
 
     BATCH_HIP(batch, hipSetDevice(batch->device));
-    if (!grow(batch->find_table, batch->find_table_bytes, table_bytes, 1) ||
-        !grow(batch->find_counts, batch->find_counts_n, counts_n, sizeof(uint32_t)) ||
-        (matches_out && !grow(batch->find_matches, batch->find_matches_n, matches_n, sizeof(unsigned long long))))
+    const char* const label = "gol_find_batch: hipFree";
+    if (!batch->find.table.grow(table_bytes, label) || !batch->find.counts.grow(counts_n, label) ||
+        (matches_out && !batch->find.matches.grow(matches_n, label)))
         return batch_err(batch, GOL_ENOMEM, "gol_find_batch: hipMalloc of the pattern table (%zu bytes), the counts "
                          "(%zu entries) or the match planes (%zu entries) failed; nothing written", table_bytes,
                          counts_n, matches_out ? matches_n : (size_t)0);
     // `table` outlives the copy: the call synchronises before it returns
-    BATCH_HIP(batch, hipMemcpyAsync(batch->find_table, table.data(), table_bytes, hipMemcpyHostToDevice, batch->stream));
-    golbatch::FindParams fp{};
-    fp.plane = batch->plane;
-    fp.counts = batch->find_counts;
-    fp.matches = matches_out ? batch->find_matches : nullptr;
-    fp.boards = batch->geo.boards;
-    fp.width = batch->geo.width;
-    fp.height = batch->geo.height;
-    fp.boards_per_wave = batch->lanes.boards_per_wave;
+    BATCH_HIP(batch, hipMemcpyAsync(batch->find.table.dev, table.data(), table_bytes, hipMemcpyHostToDevice, batch->stream));
+    auto fp = launch_params<golbatch::FindParams>(batch);
+    fp.plane = batch->plane.dev;
+    fp.counts = batch->find.counts.dev;
+    fp.matches = matches_out ? batch->find.matches.dev : nullptr;
     fp.npatterns = npatterns;
-    const auto* dev_heads = static_cast<const golbatch::FindPattern*>(batch->find_table);
-    const auto* dev_rows = reinterpret_cast<const unsigned long long*>(
-        static_cast<const unsigned char*>(batch->find_table) + head_bytes);
+    const auto* dev_heads = reinterpret_cast<const golbatch::FindPattern*>(batch->find.table.dev);
+    const auto* dev_rows = reinterpret_cast<const unsigned long long*>(batch->find.table.dev + head_bytes);
     // the cut: as many patterns per launch as stay within the bound, one at least
-    const uint64_t cut = batch->find_cut ? batch->find_cut : golbatch::kAutoFindCut;
-    batch->find_launches = 0;
-    batch->find_cared = cared_all;
+    const uint64_t cut = batch->find.cut ? batch->find.cut : golbatch::kAutoFindCut;
+    batch->find.launches = 0;
+    batch->find.cared = cared_all;
     for (int32_t first = 0; first < npatterns; first += fp.count) {
         uint64_t cared = heads[first].cared;
         int32_t n = 1;
@@ -567,12 +567,12 @@ int gol_find_batch(gol_batch* batch, const gol_batch_pattern* patterns, int32_t 
         fp.first = first;
         fp.count = n;
         BATCH_HIP(batch, golbatch::launch_batch_find(fp, dev_heads, dev_rows, batch->geo.clipped, batch->stream));
-        ++batch->find_launches;
+        ++batch->find.launches;
     }
-    BATCH_HIP(batch, hipMemcpyAsync(counts_out, batch->find_counts, counts_n * sizeof(uint32_t), hipMemcpyDeviceToHost,
+    BATCH_HIP(batch, hipMemcpyAsync(counts_out, batch->find.counts.dev, counts_n * sizeof(uint32_t), hipMemcpyDeviceToHost,
                                     batch->stream));
     if (matches_out)
-        BATCH_HIP(batch, hipMemcpyAsync(matches_out, batch->find_matches, matches_n * sizeof(uint64_t),
+        BATCH_HIP(batch, hipMemcpyAsync(matches_out, batch->find.matches.dev, matches_n * sizeof(uint64_t),
                                         hipMemcpyDeviceToHost, batch->stream));
     BATCH_HIP(batch, hipStreamSynchronize(batch->stream));
     return GOL_OK;
@@ -580,14 +580,14 @@ int gol_find_batch(gol_batch* batch, const gol_batch_pattern* patterns, int32_t 
 
 int gol_find_batch_set_cut(gol_batch* batch, uint32_t cared_cells_per_launch) {
     if (!batch) return batch_err(nullptr, GOL_EINVAL, "gol_find_batch_set_cut: null handle");
-    batch->find_cut = cared_cells_per_launch;
+    batch->find.cut = cared_cells_per_launch;
     return GOL_OK;
 }
 
 int gol_find_batch_stats(gol_batch* batch, uint64_t* launches, uint64_t* cared_cells) {
     if (!batch) return batch_err(nullptr, GOL_EINVAL, "gol_find_batch_stats: null handle");
-    if (launches) *launches = batch->find_launches;
-    if (cared_cells) *cared_cells = batch->find_cared;
+    if (launches) *launches = batch->find.launches;
+    if (cared_cells) *cared_cells = batch->find.cared;
     return GOL_OK;
 }
 
@@ -595,9 +595,7 @@ int gol_objects_batch_check(const gol_batch_config* cfg, int64_t first, int64_t 
                             int32_t max_objects) {
     if (!cfg) return batch_err(nullptr, GOL_EINVAL, "gol_objects_batch_check: null configuration");
     golbatch::Geometry g;
-    if (const char* why = golbatch::batch_geometry(*cfg, &g))
-        return batch_err(nullptr, GOL_EINVAL, "batch of %d boards %d x %d: %s", cfg->boards, cfg->width, cfg->height,
-                         why);
+    if (const int rc = config_geometry(cfg, &g)) return rc;
     if (const char* why = golbatch::batch_objects_args(g, first, count, reach, max_objects))
         return batch_err(nullptr, GOL_EINVAL, "gol_objects_batch_check: %s (first %lld, count %lld, reach %d, "
                          "max_objects %d, batch of %d)", why, (long long)first, (long long)count, reach, max_objects,
@@ -626,34 +624,32 @@ int gol_objects_batch(gol_batch* batch, int64_t first, int64_t count, int32_t re
 
     BATCH_HIP(batch, hipSetDevice(batch->device));
     if (const int rc = launch_objects(batch, "gol_objects_batch", first, count, reach, max_objects)) return rc;
-    BATCH_HIP(batch, hipMemcpyAsync(counts_out, batch->obj_counts, n * sizeof(uint32_t), hipMemcpyDeviceToHost,
+    BATCH_HIP(batch, hipMemcpyAsync(counts_out, batch->objects.counts.dev, n * sizeof(uint32_t), hipMemcpyDeviceToHost,
                                     batch->stream));
-    BATCH_HIP(batch, hipMemcpyAsync(objects_out, batch->obj_records, records_n * sizeof(gol_batch_object),
+    BATCH_HIP(batch, hipMemcpyAsync(objects_out, batch->objects.records.dev, records_n * sizeof(gol_batch_object),
                                     hipMemcpyDeviceToHost, batch->stream));
     BATCH_HIP(batch, hipStreamSynchronize(batch->stream));
-    batch->obj_launches = 1;
-    batch->obj_total = batch->obj_truncated = 0;
+    batch->objects.launches = 1;
+    batch->objects.total = batch->objects.truncated = 0;
     for (size_t i = 0; i < n; ++i) {
-        batch->obj_total += counts_out[i];
-        batch->obj_truncated += counts_out[i] > (uint32_t)max_objects ? 1u : 0u;
+        batch->objects.total += counts_out[i];
+        batch->objects.truncated += counts_out[i] > (uint32_t)max_objects ? 1u : 0u;
     }
     return GOL_OK;
 }
 
 int gol_objects_batch_stats(gol_batch* batch, uint64_t* launches, uint64_t* objects, uint64_t* boards_truncated) {
     if (!batch) return batch_err(nullptr, GOL_EINVAL, "gol_objects_batch_stats: null handle");
-    if (launches) *launches = batch->obj_launches;
-    if (objects) *objects = batch->obj_total;
-    if (boards_truncated) *boards_truncated = batch->obj_truncated;
+    if (launches) *launches = batch->objects.launches;
+    if (objects) *objects = batch->objects.total;
+    if (boards_truncated) *boards_truncated = batch->objects.truncated;
     return GOL_OK;
 }
 
 int gol_census_batch_check(const gol_batch_config* cfg, int32_t reach, int32_t max_objects, int64_t max_keys) {
     if (!cfg) return batch_err(nullptr, GOL_EINVAL, "gol_census_batch_check: null configuration");
     golbatch::Geometry g;
-    if (const char* why = golbatch::batch_geometry(*cfg, &g))
-        return batch_err(nullptr, GOL_EINVAL, "batch of %d boards %d x %d: %s", cfg->boards, cfg->width, cfg->height,
-                         why);
+    if (const int rc = config_geometry(cfg, &g)) return rc;
     golbatch::CensusRequest r{};
     r.call = golbatch::CensusRequest::kCheck;
     r.reach = reach;
@@ -675,26 +671,23 @@ int gol_census_batch_begin(gol_batch* batch, int64_t max_keys) {
         return batch_err(batch, GOL_EINVAL, "gol_census_batch_begin: %s (max_keys %lld)", why, (long long)max_keys);
     const uint32_t capacity = golbatch::census_capacity(max_keys);
     BATCH_HIP(batch, hipSetDevice(batch->device));
-    // what is missing is allocated before anything of the handle changes
-    void* slots = nullptr;
-    void* counters = nullptr;
-    const size_t bytes = (size_t)capacity * sizeof(gol_census_entry);
-    if ((capacity != batch->census_capacity && hipMalloc(&slots, bytes) != hipSuccess) ||
-        (!batch->census_counters &&
-         hipMalloc(&counters, golbatch::kCensusCounters * sizeof(unsigned long long)) != hipSuccess)) {
-        (void)hipGetLastError();
-        if (slots) hip_note(hipFree(slots), "gol_census_batch_begin: hipFree");
+    // what is missing (a table of another size, smaller ones too: the capacity is the probe mask) is allocated
+    // before anything of the handle changes, and swapped in once all of it is there
+    const char* const label = "gol_census_batch_begin: hipFree";
+    DevBuf<unsigned long long> slots, counters;
+    if ((capacity != batch->census.capacity() && !slots.grow(4 * (size_t)capacity, label)) ||
+        (!batch->census.counters.dev && !counters.grow(golbatch::kCensusCounters, label))) {
+        slots.release(label);
         return batch_err(batch, GOL_ENOMEM, "gol_census_batch_begin: hipMalloc of %zu bytes for a table of %u slots "
-                         "failed; nothing changed", bytes, capacity);
+                         "failed; nothing changed", (size_t)capacity * sizeof(gol_census_entry), capacity);
     }
-    if (counters) batch->census_counters = static_cast<unsigned long long*>(counters);
-    if (slots) {  // nothing is in flight on the old table: every call synchronises
-        if (batch->census_slots) hip_note(hipFree(batch->census_slots), "gol_census_batch_begin: hipFree");
-        batch->census_slots = static_cast<unsigned long long*>(slots);
-        batch->census_capacity = capacity;
+    if (counters.dev) batch->census.counters.swap(counters);
+    if (slots.dev) {  // nothing is in flight on the old table: every call synchronises
+        batch->census.slots.swap(slots);
+        slots.release(label);
     }
-    batch->census_calls = 0;
-    BATCH_HIP(batch, golbatch::launch_census_clear(census_table(batch), batch->stream));
+    batch->census.calls = 0;
+    BATCH_HIP(batch, golbatch::launch_census_clear(batch->census.table(), batch->stream));
     BATCH_HIP(batch, hipStreamSynchronize(batch->stream));
     return GOL_OK;
 }
@@ -712,16 +705,16 @@ int gol_census_batch_add(gol_batch* batch, int32_t reach, int32_t max_objects, u
     if (const int rc = launch_objects(batch, "gol_census_batch_add", 0, batch->geo.boards, reach, max_objects))
         return rc;
     golbatch::CensusTallyParams p{};
-    p.records = reinterpret_cast<const uint4*>(batch->obj_records);
-    p.counts = batch->obj_counts;
-    p.table = census_table(batch);
+    p.records = reinterpret_cast<const uint4*>(batch->objects.records.dev);
+    p.counts = batch->objects.counts.dev;
+    p.table = batch->census.table();
     p.total = (uint64_t)batch->geo.boards * (uint64_t)max_objects;
     p.max_objects = (uint32_t)max_objects;
-    p.call = (uint32_t)batch->census_calls;
+    p.call = (uint32_t)batch->census.calls;
     BATCH_HIP(batch, golbatch::launch_census_tally(p, batch->stream));
     BATCH_HIP(batch, hipStreamSynchronize(batch->stream));
     if (call_out) *call_out = p.call;
-    ++batch->census_calls;
+    ++batch->census.calls;
     return GOL_OK;
 }
 
@@ -735,18 +728,18 @@ int gol_census_batch_add_records(gol_batch* batch, const gol_batch_object* recor
     r.board = board;
     if (const char* why = census_refusal(batch, r))
         return batch_err(batch, GOL_EINVAL, "gol_census_batch_add_records: %s (n %zu, board %u)", why, n, board);
-    const uint32_t call = (uint32_t)batch->census_calls;
+    const uint32_t call = (uint32_t)batch->census.calls;
     if (n > 0) {
         BATCH_HIP(batch, hipSetDevice(batch->device));
-        if (!grow(batch->census_in, batch->census_in_n, n, sizeof(gol_batch_object)))
+        if (!batch->census.in.grow(n, "gol_census_batch_add_records: hipFree"))
             return batch_err(batch, GOL_ENOMEM, "gol_census_batch_add_records: hipMalloc for %zu records failed; "
                              "nothing tallied", n);
         // `records` outlives the copy: the call synchronises before it returns
-        BATCH_HIP(batch, hipMemcpyAsync(batch->census_in, records, n * sizeof(gol_batch_object), hipMemcpyHostToDevice,
+        BATCH_HIP(batch, hipMemcpyAsync(batch->census.in.dev, records, n * sizeof(gol_batch_object), hipMemcpyHostToDevice,
                                         batch->stream));
         golbatch::CensusTallyParams p{};
-        p.records = reinterpret_cast<const uint4*>(batch->census_in);
-        p.table = census_table(batch);
+        p.records = reinterpret_cast<const uint4*>(batch->census.in.dev);
+        p.table = batch->census.table();
         p.total = n;
         p.board = board;
         p.call = call;
@@ -754,7 +747,7 @@ int gol_census_batch_add_records(gol_batch* batch, const gol_batch_object* recor
         BATCH_HIP(batch, hipStreamSynchronize(batch->stream));
     }
     if (call_out) *call_out = call;
-    ++batch->census_calls;
+    ++batch->census.calls;
     return GOL_OK;
 }
 
@@ -764,29 +757,26 @@ int gol_census_batch_read(gol_batch* batch, gol_census_entry* entries_out, size_
     r.call = golbatch::CensusRequest::kRead;
     if (const char* why = census_refusal(batch, r)) return batch_err(batch, GOL_EINVAL, "gol_census_batch_read: %s", why);
     if (!n_out) return batch_err(batch, GOL_EINVAL, "gol_census_batch_read: n_out is null");
-    BATCH_HIP(batch, hipSetDevice(batch->device));
     unsigned long long counters[golbatch::kCensusCounters];
-    BATCH_HIP(batch, hipMemcpyAsync(counters, batch->census_counters, sizeof counters, hipMemcpyDeviceToHost,
-                                    batch->stream));
-    BATCH_HIP(batch, hipStreamSynchronize(batch->stream));
+    if (const int rc = census_counters(batch, counters)) return rc;
     const size_t n = (size_t)counters[golbatch::kCensusDistinct];
     *n_out = n;
     if (capacity < n || (n > 0 && !entries_out))
         return batch_err(batch, GOL_EINVAL, "gol_census_batch_read: entries_out holds %zu entries, the census has %zu "
                          "distinct keys", entries_out ? capacity : (size_t)0, n);
     if (n == 0) return GOL_OK;
-    if (!grow(batch->census_out, batch->census_out_n, n, sizeof(gol_census_entry)))
+    if (!batch->census.out.grow(n, "gol_census_batch_read: hipFree"))
         return batch_err(batch, GOL_ENOMEM, "gol_census_batch_read: hipMalloc for %zu entries failed; nothing written",
                          n);
-    BATCH_HIP(batch, hipMemsetAsync(batch->census_counters + golbatch::kCensusCompacted, 0, sizeof(unsigned long long),
+    BATCH_HIP(batch, hipMemsetAsync(batch->census.counters.dev + golbatch::kCensusCompacted, 0, sizeof(unsigned long long),
                                     batch->stream));
-    BATCH_HIP(batch, golbatch::launch_census_compact(census_table(batch), reinterpret_cast<uint4*>(batch->census_out),
+    BATCH_HIP(batch, golbatch::launch_census_compact(batch->census.table(), reinterpret_cast<uint4*>(batch->census.out.dev),
                                                      n, batch->stream));
     std::vector<gol_census_entry> got(n);
     unsigned long long compacted = 0;
-    BATCH_HIP(batch, hipMemcpyAsync(got.data(), batch->census_out, n * sizeof(gol_census_entry), hipMemcpyDeviceToHost,
+    BATCH_HIP(batch, hipMemcpyAsync(got.data(), batch->census.out.dev, n * sizeof(gol_census_entry), hipMemcpyDeviceToHost,
                                     batch->stream));
-    BATCH_HIP(batch, hipMemcpyAsync(&compacted, batch->census_counters + golbatch::kCensusCompacted, sizeof compacted,
+    BATCH_HIP(batch, hipMemcpyAsync(&compacted, batch->census.counters.dev + golbatch::kCensusCompacted, sizeof compacted,
                                     hipMemcpyDeviceToHost, batch->stream));
     BATCH_HIP(batch, hipStreamSynchronize(batch->stream));
     if (compacted != n)
@@ -807,13 +797,9 @@ int gol_census_batch_stats(gol_batch* batch, uint64_t* calls, uint64_t* seen, ui
                            uint64_t* overflowed, uint64_t* distinct) {
     if (!batch) return batch_err(nullptr, GOL_EINVAL, "gol_census_batch_stats: null handle");
     unsigned long long counters[golbatch::kCensusCounters] = {};
-    if (batch->census_capacity != 0) {
-        BATCH_HIP(batch, hipSetDevice(batch->device));
-        BATCH_HIP(batch, hipMemcpyAsync(counters, batch->census_counters, sizeof counters, hipMemcpyDeviceToHost,
-                                        batch->stream));
-        BATCH_HIP(batch, hipStreamSynchronize(batch->stream));
-    }
-    if (calls) *calls = batch->census_calls;
+    if (batch->census.capacity() != 0)
+        if (const int rc = census_counters(batch, counters)) return rc;
+    if (calls) *calls = batch->census.calls;
     if (seen) *seen = counters[golbatch::kCensusSeen];
     if (tallied) *tallied = counters[golbatch::kCensusTallied];
     if (truncated) *truncated = counters[golbatch::kCensusTruncated];
@@ -825,9 +811,7 @@ int gol_census_batch_stats(gol_batch* batch, uint64_t* calls, uint64_t* seen, ui
 int gol_rules_batch_check(const gol_batch_config* cfg, int64_t first, int64_t count, const uint32_t* rules) {
     if (!cfg) return batch_err(nullptr, GOL_EINVAL, "gol_rules_batch_check: null configuration");
     golbatch::Geometry g;
-    if (const char* why = golbatch::batch_geometry(*cfg, &g))
-        return batch_err(nullptr, GOL_EINVAL, "batch of %d boards %d x %d: %s", cfg->boards, cfg->width, cfg->height,
-                         why);
+    if (const int rc = config_geometry(cfg, &g)) return rc;
     int64_t which = -1;
     if (const char* why = golbatch::batch_rules_args(g, first, count, rules, &which))
         return rules_refusal(nullptr, "gol_rules_batch_check", why, g, first, count, rules, which);
@@ -842,44 +826,36 @@ int gol_rules_batch_set(gol_batch* batch, int64_t first, int64_t count, const ui
     const size_t boards = (size_t)batch->geo.boards;
     const uint32_t config_word = golbatch::rule_word(batch->birth, batch->survive);
     if (!rules) {  // the whole batch back to its configuration's rule; the device words stay for a later set
-        batch->rules_on = false;
-        std::fill(batch->rules_host.begin(), batch->rules_host.end(), config_word);
+        batch->rules.on = false;
+        std::fill(batch->rules.host.begin(), batch->rules.host.end(), config_word);
         return GOL_OK;
     }
     BATCH_HIP(batch, hipSetDevice(batch->device));
-    if (!batch->rules) {
-        void* words = nullptr;
-        if (hipMalloc(&words, boards * sizeof(uint32_t)) != hipSuccess) {
-            (void)hipGetLastError();
-            return batch_err(batch, GOL_ENOMEM, "gol_rules_batch_set: hipMalloc of %zu bytes for the rule words failed; "
-                             "nothing changed", boards * sizeof(uint32_t));
-        }
-        batch->rules = static_cast<uint32_t*>(words);
-    }
+    if (!batch->rules.words.grow(boards, "gol_rules_batch_set: hipFree"))
+        return batch_err(batch, GOL_ENOMEM, "gol_rules_batch_set: hipMalloc of %zu bytes for the rule words failed; "
+                         "nothing changed", boards * sizeof(uint32_t));
     // the device takes a copy of what the rules will be; the handle changes once it has arrived
-    std::vector<uint32_t> next = batch->rules_host;
+    std::vector<uint32_t> next = batch->rules.host;
     if (next.empty()) next.assign(boards, config_word);
     std::copy(rules, rules + count, next.begin() + first);
     // while the configuration's rule is in force the device words are stale (or new): all of them go
-    const size_t lo = batch->rules_on ? (size_t)first : 0, n = batch->rules_on ? (size_t)count : boards;
-    BATCH_HIP(batch, hipMemcpyAsync(batch->rules + lo, next.data() + lo, n * sizeof(uint32_t), hipMemcpyHostToDevice,
+    const size_t lo = batch->rules.on ? (size_t)first : 0, n = batch->rules.on ? (size_t)count : boards;
+    BATCH_HIP(batch, hipMemcpyAsync(batch->rules.words.dev + lo, next.data() + lo, n * sizeof(uint32_t), hipMemcpyHostToDevice,
                                     batch->stream));
     BATCH_HIP(batch, hipStreamSynchronize(batch->stream));
-    batch->rules_host.swap(next);
-    batch->rules_on = true;
+    batch->rules.host.swap(next);
+    batch->rules.on = true;
     return GOL_OK;
 }
 
 int gol_rules_batch_get(gol_batch* batch, int64_t first, int64_t count, uint32_t* rules_out) {
     if (!batch) return batch_err(nullptr, GOL_EINVAL, "gol_rules_batch_get: null handle");
     if (!rules_out) return batch_err(batch, GOL_EINVAL, "gol_rules_batch_get: rules_out is null");
-    if (!window_ok(batch, first, count))
-        return batch_err(batch, GOL_EINVAL, "gol_rules_batch_get: boards [%lld, %lld + %lld) outside the batch of %d",
-                         (long long)first, (long long)first, (long long)count, batch->geo.boards);
-    if (batch->rules_host.empty())
+    if (!golbatch::window_ok(batch->geo, first, count)) return window_refusal(batch, "gol_rules_batch_get", first, count);
+    if (batch->rules.host.empty())
         std::fill(rules_out, rules_out + count, golbatch::rule_word(batch->birth, batch->survive));
     else
-        std::copy(batch->rules_host.begin() + first, batch->rules_host.begin() + first + count, rules_out);
+        std::copy(batch->rules.host.begin() + first, batch->rules.host.begin() + first + count, rules_out);
     return GOL_OK;
 }
 

@@ -1,7 +1,8 @@
 // gol_batch.h -- internal interface between the batch engine's C-ABI unit
-// (gol_batch.cpp) and its gfx950 kernels (gol_batch.hip); DESIGN.md section
-// 5f.  A header of its own: the step kernels' units include none of it.  Not
-// installed.
+// (gol_batch.cpp) and its gfx950 kernels (gol_batch*.hip); DESIGN.md sections
+// 5f to 5k: the lane mapping, the pure validators, the launch parameters and
+// what every launcher checks of them.  A header of its own: the step kernels'
+// units include none of it.  Not installed.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -27,6 +28,18 @@ struct Lanes {
 inline Lanes batch_lanes(int32_t height, int64_t boards) {
     const int32_t k = kLanes / height;
     return {k, (boards + k - 1) / k};
+}
+
+// What every per-board launcher checks of its parameters before its own: with
+// it, the lane mapping's indices stay inside `boards` boards of `height` rows.
+inline bool launch_geometry_ok(int32_t boards, int32_t width, int32_t height, int32_t boards_per_wave,
+                               bool clipped = false, int32_t vis_w = 1, int32_t vis_h = 1) {
+    return boards >= 1 && boards <= kMaxBoards && width >= 1 && width <= kLanes && height >= 1 && height <= kLanes &&
+           boards_per_wave == batch_lanes(height, boards).boards_per_wave && (!clipped || (vis_w >= 1 && vis_h >= 1));
+}
+// ... and the grid it launches: workgroups of kWavesPerWG waves for `boards` boards.
+inline dim3 launch_grid(int32_t height, int64_t boards) {
+    return dim3((unsigned)((batch_lanes(height, boards).waves + kWavesPerWG - 1) / kWavesPerWG));
 }
 
 // The geometry a batch runs with, or the reason it is refused (null: fine).
@@ -57,6 +70,11 @@ inline const char* batch_geometry(const gol_batch_config& c, Geometry* g) {
     }
     *g = {c.boards, c.width, c.height, vw, vh, clipped};
     return nullptr;
+}
+
+// boards [first, first + count) inside the batch
+inline bool window_ok(const Geometry& g, int64_t first, int64_t count) {
+    return first >= 0 && count >= 1 && first < g.boards && count <= (int64_t)g.boards - first;
 }
 
 // Device memory of a batch: the plane, the plane of the generation before it
@@ -129,8 +147,7 @@ inline uint32_t rule_word(uint32_t birth, uint32_t survive) { return GOL_BATCH_R
 inline const char* batch_rules_args(const Geometry& g, int64_t first, int64_t count, const uint32_t* rules,
                                     int64_t* which) {
     *which = -1;
-    if (first < 0 || count < 1 || first >= g.boards || count > (int64_t)g.boards - first)
-        return "boards [first, first + count) outside the batch";
+    if (!window_ok(g, first, count)) return "boards [first, first + count) outside the batch";
     if (!rules) return first == 0 && count == g.boards ? nullptr : "rules is null for a part of the batch";
     for (int64_t j = 0; j < count; ++j)
         if (rules[j] & ~kRuleWordBits) {
@@ -214,8 +231,7 @@ inline const char* batch_objects_args(const Geometry& g, int64_t first, int64_t 
                                       int32_t max_objects) {
     if (reach != 1 && reach != 2) return "reach must be 1 or 2";
     if (max_objects < 1 || max_objects > kMaxBoardObjects) return "max_objects must be 1 .. 1024";
-    if (first < 0 || count < 1 || first >= g.boards || count > (int64_t)g.boards - first)
-        return "boards [first, first + count) outside the batch";
+    if (!window_ok(g, first, count)) return "boards [first, first + count) outside the batch";
     return nullptr;
 }
 

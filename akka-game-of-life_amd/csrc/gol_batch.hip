@@ -19,7 +19,8 @@
 //                         (column sums first, as step_kernel);
 //   population (POP)      popcount of the lane's row, a DPP prefix sum over
 //                         the wave, one permute: the board's last lane
-//                         subtracts the prefix before its board and stores;
+//                         subtracts the prefix before its board and stores
+//                         (gol_batch_wave.h's BoardSum);
 //   settle (SETTLE)       the row against the row of two generations ago, a
 //                         ballot masked to the board's lanes.
 // The generation itself is gol_batch_gen.h's, shared with batch_cycle_kernel
@@ -39,28 +40,6 @@ namespace golbatch {
 
 namespace {
 
-constexpr int kDppRowShr = 0x110;     // row_shr:n = kDppRowShr + n (rows of 16 lanes)
-constexpr int kDppRowBcast15 = 0x142;  // lane 15 of each row -> the next row
-constexpr int kDppRowBcast31 = 0x143;  // lane 31 -> rows 2 and 3
-
-// v + (v of the DPP source lane, 0 where there is none or the row is masked out)
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ uint32_t dpp_add(uint32_t v) {
-    return v + (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, ROW_MASK, 0xf, false);
-}
-
-// Inclusive prefix sum over the wave's 64 lanes: four shifts inside the rows
-// of 16, then the two row broadcasts.
-__device__ __forceinline__ uint32_t wave_prefix_sum(uint32_t v) {
-    v = dpp_add<kDppRowShr + 1, 0xf>(v);
-    v = dpp_add<kDppRowShr + 2, 0xf>(v);
-    v = dpp_add<kDppRowShr + 4, 0xf>(v);
-    v = dpp_add<kDppRowShr + 8, 0xf>(v);
-    v = dpp_add<kDppRowBcast15, 0xa>(v);
-    v = dpp_add<kDppRowBcast31, 0xc>(v);
-    return v;
-}
-
 // The rule a RULES instance hands the generation in p's place (P: birth, survive).
 struct RuleMasks {
     uint32_t birth, survive;
@@ -74,9 +53,7 @@ template <bool LIFE, bool CLIPPED, bool POP, bool SETTLE, bool RULES = false>
 __global__ __launch_bounds__(kLanes* kWavesPerWG) void batch_step_kernel(const StepParams p) {
     static_assert(!(RULES && LIFE), "the RULES instances are generic");
     const int lane = threadIdx.x & (kLanes - 1);
-    const int wave_in_wg = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / kLanes));
-    const int32_t wave = (int32_t)blockIdx.x * kWavesPerWG + wave_in_wg;  // waves <= boards <= 2^22
-    const int32_t board0 = wave * p.boards_per_wave;
+    const int32_t board0 = wave_index() * p.boards_per_wave;
     if (board0 >= p.boards) return;  // the grid's last workgroup: wave-uniform, and nothing below synchronises
     const int H = p.height;
     const int bl = lane / H, y = lane - bl * H;
@@ -102,12 +79,7 @@ __global__ __launch_bounds__(kLanes* kWavesPerWG) void batch_step_kernel(const S
     const int up_addr = 4 * (active ? (y > 0 ? lane - 1 : lane + H - 1) : lane);
     const int dn_addr = 4 * (active ? (y < H - 1 ? lane + 1 : lane - (H - 1)) : lane);
     const GenConsts C{wm_lo, wm_hi, wsh, sm_lo, sm_hi, upm, dnm, up_addr, dn_addr};
-    // population: the board's last lane stores; the prefix before the board is the one of the lane before its
-    // first (none before lane 0)
-    const bool writer = active && y == H - 1;
-    const int first_lane = lane - (H - 1);
-    const int before_addr = 4 * (writer && first_lane > 0 ? first_lane - 1 : lane);
-    const bool has_before = writer && first_lane > 0;
+    const BoardSum S(active, lane, y, H);  // population: the board's last lane stores
     // settle: the board's lanes in a ballot
     unsigned long long bm = ~0ull;
     if constexpr (SETTLE) {
@@ -141,9 +113,8 @@ __global__ __launch_bounds__(kLanes* kWavesPerWG) void batch_step_kernel(const S
             const Row nx = generation<LIFE, CLIPPED, ROT, NARROW>(R, C, cur);
             if constexpr (POP) {
                 const uint32_t bits = (uint32_t)__builtin_popcount(nx.lo) + (NARROW ? 0u : (uint32_t)__builtin_popcount(nx.hi));
-                const uint32_t incl = wave_prefix_sum(active ? bits : 0u);
-                const uint32_t before = lane_read(before_addr, incl);
-                if (writer) p.pops[(size_t)board * p.pop_stride + g] = incl - (has_before ? before : 0u);
+                const uint32_t pop = S.total(active ? bits : 0u);
+                if (S.writer) p.pops[(size_t)board * p.pop_stride + g] = pop;
             }
             if constexpr (SETTLE) {
                 const unsigned long long same = __ballot(nx.lo == prev.lo && (NARROW || nx.hi == prev.hi));
@@ -200,9 +171,7 @@ template <bool LIFE, bool CLIPPED, bool RULES = false>
 __global__ __launch_bounds__(kLanes* kWavesPerWG) void batch_cycle_kernel(const CycleParams p) {
     static_assert(!(RULES && LIFE), "the RULES instances are generic");
     const int lane = threadIdx.x & (kLanes - 1);
-    const int wave_in_wg = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / kLanes));
-    const int32_t wave = (int32_t)blockIdx.x * kWavesPerWG + wave_in_wg;  // waves <= boards <= 2^22
-    const int32_t board0 = wave * p.boards_per_wave;
+    const int32_t board0 = wave_index() * p.boards_per_wave;
     if (board0 >= p.boards) return;  // the grid's last workgroup: wave-uniform, and nothing below synchronises
     const Lane L = lane_of<CLIPPED>(p, lane, board0);
     const GenConsts C = L.consts();
@@ -347,13 +316,11 @@ hipError_t launch_step_flags(const StepParams& p, dim3 grid, hipStream_t stream)
 
 hipError_t launch_batch_step(const StepParams& p, bool life, bool clipped, bool rules, hipStream_t stream) {
     // every index the kernel forms stays inside the plane, the series, the settle words and the rule words
-    if (rules != (p.rules != nullptr) ||
-        !p.plane || p.boards < 1 || p.boards > kMaxBoards || p.width < 1 || p.width > kLanes || p.height < 1 ||
-        p.height > kLanes || p.boards_per_wave != batch_lanes(p.height, p.boards).boards_per_wave || p.gens < 1 ||
-        (p.pops && p.pop_stride < p.gens) || (p.settled && !p.prev) || (clipped && (p.vis_w < 1 || p.vis_h < 1)))
+    if (!launch_geometry_ok(p.boards, p.width, p.height, p.boards_per_wave, clipped, p.vis_w, p.vis_h) ||
+        rules != (p.rules != nullptr) || !p.plane || p.gens < 1 || (p.pops && p.pop_stride < p.gens) ||
+        (p.settled && !p.prev))
         return hipErrorInvalidValue;
-    const int64_t waves = batch_lanes(p.height, p.boards).waves;
-    const dim3 grid((unsigned)((waves + kWavesPerWG - 1) / kWavesPerWG));
+    const dim3 grid = launch_grid(p.height, p.boards);
     if (rules)
         return clipped ? launch_step_flags<false, true, true>(p, grid, stream)
                        : launch_step_flags<false, false, true>(p, grid, stream);
@@ -363,15 +330,11 @@ hipError_t launch_batch_step(const StepParams& p, bool life, bool clipped, bool 
 
 hipError_t launch_batch_cycle(const CycleParams& p, bool life, bool clipped, bool rules, hipStream_t stream) {
     // every index the kernel forms stays inside the two planes, the per-board words and the rule words
-    if (rules != (p.rules != nullptr) ||
-        !p.plane || !p.snap || !p.period || !p.seen || !p.counters || p.boards < 1 || p.boards > kMaxBoards ||
-        p.width < 1 || p.width > kLanes || p.height < 1 || p.height > kLanes ||
-        p.boards_per_wave != batch_lanes(p.height, p.boards).boards_per_wave || p.gens < 1 ||
-        p.gens > UINT32_MAX - p.g0 ||
-        (clipped && (p.vis_w < 1 || p.vis_h < 1)))
+    if (!launch_geometry_ok(p.boards, p.width, p.height, p.boards_per_wave, clipped, p.vis_w, p.vis_h) ||
+        rules != (p.rules != nullptr) || !p.plane || !p.snap || !p.period || !p.seen || !p.counters || p.gens < 1 ||
+        p.gens > UINT32_MAX - p.g0)
         return hipErrorInvalidValue;
-    const int64_t waves = batch_lanes(p.height, p.boards).waves;
-    const dim3 grid((unsigned)((waves + kWavesPerWG - 1) / kWavesPerWG)), block(kLanes * kWavesPerWG);
+    const dim3 grid = launch_grid(p.height, p.boards), block(kLanes * kWavesPerWG);
     if (rules)
         return clipped ? gol::launch_kernel(batch_cycle_kernel<false, true, true>, grid, block, stream, p)
                        : gol::launch_kernel(batch_cycle_kernel<false, false, true>, grid, block, stream, p);

@@ -1,9 +1,9 @@
 // gol_batch_census.hip -- the census of a batch's objects (gol_census_batch_*
 // in gol_batch.cpp): a hash table in device memory that
 // counts the objects of every key (hash, w, h, population) over as many calls
-// as the caller likes and keeps each key's earliest place.  A unit of its own:
-// gol_batch.hip, gol_batch_find.hip and gol_batch_objects.hip are compiled as
-// they were.
+// as the caller likes and keeps each key's earliest place.  A unit of its own,
+// without the stencil: of the batch's device headers it takes gol_batch_wave.h
+// (the wave's prefix sum) alone.
 //
 // The table.  capacity slots (a power of two) of four qwords:
 //   A      hash[47:0] << 1 | 1
@@ -44,6 +44,7 @@
 //
 // No LDS, no scratch; vector atomics at device scope only.
 #include "gol_batch.h"
+#include "gol_batch_wave.h"
 #include "gol_kernels.h"
 
 namespace golbatch {
@@ -52,14 +53,6 @@ namespace {
 
 using u64 = unsigned long long;
 
-constexpr int kDppRowShr = 0x110;      // row_shr:n = kDppRowShr + n (rows of 16 lanes)
-constexpr int kDppRowBcast15 = 0x142;  // lane 15 of each row -> the next row
-constexpr int kDppRowBcast31 = 0x143;  // lane 31 -> rows 2 and 3
-
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ uint32_t dpp_add(uint32_t v) {
-    return v + (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, ROW_MASK, 0xf, false);
-}
 template <int CTRL, int ROW_MASK>
 __device__ __forceinline__ uint32_t dpp_min(uint32_t v) {
     const uint32_t o = (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)v, CTRL, ROW_MASK, 0xf, false);
@@ -69,13 +62,7 @@ __device__ __forceinline__ uint32_t dpp_min(uint32_t v) {
 // The sum / the minimum over the wave's 64 lanes, as a scalar.  Every lane of
 // the wave must be here.
 __device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
-    v = dpp_add<kDppRowShr + 1, 0xf>(v);
-    v = dpp_add<kDppRowShr + 2, 0xf>(v);
-    v = dpp_add<kDppRowShr + 4, 0xf>(v);
-    v = dpp_add<kDppRowShr + 8, 0xf>(v);
-    v = dpp_add<kDppRowBcast15, 0xa>(v);
-    v = dpp_add<kDppRowBcast31, 0xc>(v);
-    return (uint32_t)__builtin_amdgcn_readlane((int)v, kLanes - 1);
+    return (uint32_t)__builtin_amdgcn_readlane((int)wave_prefix_sum(v), kLanes - 1);
 }
 __device__ __forceinline__ uint32_t wave_min(uint32_t v) {
     v = dpp_min<kDppRowShr + 1, 0xf>(v);

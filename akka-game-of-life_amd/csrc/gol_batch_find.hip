@@ -2,7 +2,8 @@
 // gol_batch.cpp): a list of patterns matched against
 // every board of a batch in one launch, on the batch engine's lane mapping
 // (gol_batch.h batch_lanes: one 64-bit row per lane, k = 64 / height whole
-// boards per wave).  A unit of its own: gol_batch.hip is compiled as it was.
+// boards per wave).  A unit of its own; what it has in common with the other
+// batch units comes from gol_batch_gen.h and gol_batch_wave.h.
 //
 // batch_find_kernel: one 8-byte load per lane, then a wave-uniform loop over
 // the launch's patterns and, inside it, over a pattern's rows.  The pattern
@@ -18,9 +19,9 @@
 //               the plane holds no bit at x >= width, so cells past the board
 //               read dead), inv all ones where the pattern cell is dead.
 //   early exit  when no lane of the wave has a candidate left (a ballot).
-// Per pattern: popcount of cand, batch_step_kernel's segmented sum (a DPP
-// prefix over the wave and one permute), one uint32 store by the board's last
-// lane; with match planes one 8-byte store of cand per lane.  No atomics, no
+// Per pattern: popcount of cand, batch_step_kernel's segmented sum (BoardSum:
+// a DPP prefix over the wave and one permute), one uint32 store by the board's
+// last lane; with match planes one 8-byte store of cand per lane.  No atomics, no
 // LDS allocation, no scratch.
 // Idle lanes (past k * height, or of boards past the batch) compute along with
 // cand = 0 -- no lane branch surrounds a permute or DPP operation -- and
@@ -32,36 +33,13 @@ namespace golbatch {
 
 namespace {
 
-// batch_step_kernel's inclusive prefix sum over the wave's 64 lanes (its unit
-// keeps its own copy: that unit is not to be recompiled differently)
-constexpr int kDppRowShr = 0x110;      // row_shr:n = kDppRowShr + n (rows of 16 lanes)
-constexpr int kDppRowBcast15 = 0x142;  // lane 15 of each row -> the next row
-constexpr int kDppRowBcast31 = 0x143;  // lane 31 -> rows 2 and 3
-
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ uint32_t dpp_add(uint32_t v) {
-    return v + (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, ROW_MASK, 0xf, false);
-}
-
-__device__ __forceinline__ uint32_t wave_prefix_sum(uint32_t v) {
-    v = dpp_add<kDppRowShr + 1, 0xf>(v);
-    v = dpp_add<kDppRowShr + 2, 0xf>(v);
-    v = dpp_add<kDppRowShr + 4, 0xf>(v);
-    v = dpp_add<kDppRowShr + 8, 0xf>(v);
-    v = dpp_add<kDppRowBcast15, 0xa>(v);
-    v = dpp_add<kDppRowBcast31, 0xc>(v);
-    return v;
-}
-
 template <bool CLIPPED>
 __global__ __launch_bounds__(kLanes* kWavesPerWG) void batch_find_kernel(
     const FindParams p, const FindPattern* __restrict__ patterns, const unsigned long long* __restrict__ table_rows) {
     // the table ([npatterns] headers; the row array, 2 qwords per pattern row) comes as arguments of its own that
     // nothing the kernel stores to aliases: what lets it be read with scalar loads
     const int lane = threadIdx.x & (kLanes - 1);
-    const int wave_in_wg = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / kLanes));
-    const int32_t wave = (int32_t)blockIdx.x * kWavesPerWG + wave_in_wg;  // waves <= boards <= 2^22
-    const int32_t board0 = wave * p.boards_per_wave;
+    const int32_t board0 = wave_index() * p.boards_per_wave;
     if (board0 >= p.boards) return;  // the grid's last workgroup: wave-uniform, and nothing below synchronises
     const Lane L = lane_of<false>(p, lane, board0);  // the mapping alone: the topology enters at the row fetch
     const int H = L.H;
@@ -71,11 +49,7 @@ __global__ __launch_bounds__(kLanes* kWavesPerWG) void batch_find_kernel(
     unsigned long long mine = 0ull;
     if (L.active) mine = p.plane[L.idx];
     const uint32_t mine_lo = (uint32_t)mine, mine_hi = (uint32_t)(mine >> 32);
-    // counting: the board's last lane stores; the prefix before the board is the one of the lane before its first
-    const bool writer = L.active && L.y == H - 1;
-    const int first_lane = lane - (H - 1);
-    const bool has_before = writer && first_lane > 0;
-    const int before_addr = 4 * (has_before ? first_lane - 1 : lane);
+    const BoardSum S(L.active, lane, L.y, H);  // counting: the board's last lane stores
 
     for (int32_t q = 0; q < p.count; ++q) {
         const int32_t pi = p.first + q;
@@ -111,9 +85,8 @@ __global__ __launch_bounds__(kLanes* kWavesPerWG) void batch_find_kernel(
             } while (c != 0ull);
             if (__builtin_amdgcn_ballot_w64(cand != 0ull) == 0ull) break;  // wave-uniform
         }
-        const uint32_t incl = wave_prefix_sum((uint32_t)__builtin_popcountll(cand));  // idle lanes: cand = 0
-        const uint32_t before = lane_read(before_addr, incl);
-        if (writer) p.counts[(size_t)L.board * (size_t)p.npatterns + (size_t)pi] = incl - (has_before ? before : 0u);
+        const uint32_t found = S.total((uint32_t)__builtin_popcountll(cand));  // idle lanes: cand = 0
+        if (S.writer) p.counts[(size_t)L.board * (size_t)p.npatterns + (size_t)pi] = found;
         if (p.matches != nullptr && L.active)
             p.matches[((size_t)pi * (size_t)p.boards + (size_t)L.board) * (size_t)H + (size_t)L.y] = cand;
     }
@@ -124,13 +97,11 @@ __global__ __launch_bounds__(kLanes* kWavesPerWG) void batch_find_kernel(
 hipError_t launch_batch_find(const FindParams& p, const FindPattern* patterns, const unsigned long long* rows,
                              bool clipped, hipStream_t stream) {
     // every index the kernel forms stays inside the plane, the pattern headers, the counts and the match planes
-    if (!p.plane || !patterns || !rows || !p.counts || p.boards < 1 || p.boards > kMaxBoards || p.width < 1 ||
-        p.width > kLanes || p.height < 1 || p.height > kLanes ||
-        p.boards_per_wave != batch_lanes(p.height, p.boards).boards_per_wave || p.npatterns < 1 ||
-        p.npatterns > kMaxFindPatterns || p.first < 0 || p.count < 1 || p.count > p.npatterns - p.first)
+    if (!launch_geometry_ok(p.boards, p.width, p.height, p.boards_per_wave) || !p.plane || !patterns || !rows ||
+        !p.counts || p.npatterns < 1 || p.npatterns > kMaxFindPatterns || p.first < 0 || p.count < 1 ||
+        p.count > p.npatterns - p.first)
         return hipErrorInvalidValue;
-    const int64_t waves = batch_lanes(p.height, p.boards).waves;
-    const dim3 grid((unsigned)((waves + kWavesPerWG - 1) / kWavesPerWG)), block(kLanes * kWavesPerWG);
+    const dim3 grid = launch_grid(p.height, p.boards), block(kLanes * kWavesPerWG);
     return clipped ? gol::launch_kernel(batch_find_kernel<true>, grid, block, stream, p, patterns, rows)
                    : gol::launch_kernel(batch_find_kernel<false>, grid, block, stream, p, patterns, rows);
 }

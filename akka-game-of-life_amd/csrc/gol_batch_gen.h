@@ -6,9 +6,11 @@
 // as references to the kernel's own locals, as the loop's lambda captured them
 // when the generation was written out in it: batch_step_kernel's 16 instances
 // keep their instruction streams (make asm-batch).  Device code only; not
-// installed.
+// installed.  What is not the stencil -- the wave's prefix sum, the lane read,
+// the per-board sum -- is gol_batch_wave.h's, which comes along from here.
 #pragma once
 #include "gol_batch.h"
+#include "gol_batch_wave.h"
 #include "gol_stencil.h"
 
 namespace golbatch {
@@ -19,10 +21,6 @@ struct Row {
     uint32_t lo, hi;
 };
 __device__ __forceinline__ Row row_of(uint32_t lo, uint32_t hi) { return Row{lo, hi}; }
-
-__device__ __forceinline__ uint32_t lane_read(int byte_addr, uint32_t v) {
-    return (uint32_t)__builtin_amdgcn_ds_bpermute(byte_addr, (int)v);
-}
 
 // The per-lane constants of a generation: references to the kernel's locals.
 struct GenConsts {

@@ -4,8 +4,9 @@
 // Chebyshev distance is at most `reach`, and per component one 16-byte record
 // (translation-invariant hash, bounding box, population), on the batch
 // engine's lane mapping (gol_batch.h batch_lanes: one 64-bit row per lane,
-// k = 64 / height whole boards per wave).  A unit of its own: gol_batch.hip
-// and gol_batch_find.hip are compiled as they were.
+// k = 64 / height whole boards per wave).  A unit of its own; what it has in
+// common with the other batch units comes from gol_batch_gen.h and
+// gol_batch_wave.h.
 //
 // batch_objects_kernel: one 8-byte load per lane; `rem`, the board's cells not
 // yet given to an object, stays in registers.  While any lane of the wave has
@@ -49,27 +50,6 @@
 namespace golbatch {
 
 namespace {
-
-// batch_step_kernel's inclusive prefix sum over the wave's 64 lanes (its unit
-// keeps its own copy: that unit is not to be recompiled differently)
-constexpr int kDppRowShr = 0x110;      // row_shr:n = kDppRowShr + n (rows of 16 lanes)
-constexpr int kDppRowBcast15 = 0x142;  // lane 15 of each row -> the next row
-constexpr int kDppRowBcast31 = 0x143;  // lane 31 -> rows 2 and 3
-
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ uint32_t dpp_add(uint32_t v) {
-    return v + (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, ROW_MASK, 0xf, false);
-}
-
-__device__ __forceinline__ uint32_t wave_prefix_sum(uint32_t v) {
-    v = dpp_add<kDppRowShr + 1, 0xf>(v);
-    v = dpp_add<kDppRowShr + 2, 0xf>(v);
-    v = dpp_add<kDppRowShr + 4, 0xf>(v);
-    v = dpp_add<kDppRowShr + 8, 0xf>(v);
-    v = dpp_add<kDppRowBcast15, 0xa>(v);
-    v = dpp_add<kDppRowBcast31, 0xc>(v);
-    return v;
-}
 
 using u64 = unsigned long long;
 
@@ -131,20 +111,19 @@ __device__ __forceinline__ Row dilate(const Lane& L, const Row& f, bool wide, ui
 template <bool CLIPPED>
 __global__ __launch_bounds__(kLanes* kWavesPerWG) void batch_objects_kernel(const ObjectsParams p) {
     const int lane = threadIdx.x & (kLanes - 1);
-    const int wave_in_wg = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / kLanes));
-    const int32_t wave = (int32_t)blockIdx.x * kWavesPerWG + wave_in_wg;  // waves <= boards <= 2^22
     // the waves hold the range's boards from p.first on; p.boards is the range's end
-    const int32_t board0 = p.first + wave * p.boards_per_wave;
+    const int32_t board0 = p.first + wave_index() * p.boards_per_wave;
     if (board0 >= p.boards) return;  // the grid's last workgroup: wave-uniform, and nothing below synchronises
     const Lane L = lane_of<CLIPPED>(p, lane, board0);
     const int H = L.H;
     const u64 bm = L.board_lanes();
     const int board_sh = L.active ? L.bl * H : 0;  // the board's first lane
     const bool wide = p.width > 32;
-    const bool writer = L.active && L.y == H - 1;
-    const int first_lane = lane - (H - 1);
-    const bool has_before = writer && first_lane > 0;
-    const int before_addr = 4 * (has_before ? first_lane - 1 : lane);
+    // the board's last lane sums and stores.  BoardSum's values as locals of the kernel, which the loop below
+    // captures one by one: captured as the struct, one of its moves was placed two instructions later
+    const BoardSum S(L.active, lane, L.y, H);
+    const bool writer = S.writer, has_before = S.has_before;
+    const int before_addr = S.before_addr;
     const size_t out = (size_t)(L.board - p.first);  // active lanes: < the range's boards
 
     Row rem = {0u, 0u};
@@ -205,9 +184,10 @@ __global__ __launch_bounds__(kLanes* kWavesPerWG) void batch_objects_kernel(cons
             const uint32_t ev = (u0 & 0xFFFFu) | (u1 << 16), od = (u0 >> 16) | (u1 & 0xFFFF0000u);
             const uint32_t ae = gol::hash_row_key(ty);
             const u64 term = (u64)ev * ae + (u64)od * (uint32_t)(ae + gol::kHashOddAdd);
-            // segmented sums: the board's last lane has its prefix, and reads the one before its board.  The 64-bit
-            // terms go as limbs of 16, 16 and 32 bits: 64 lanes' limbs of 16 bits sum to less than 2^22, and the
-            // upper limb is wanted modulo 2^32
+            // the board's sums, BoardSum::total's steps written out four abreast: the subtractions stay under the
+            // writer's branch below (through S.total they left it, and the kernel was scheduled differently).  The
+            // 64-bit terms go as limbs of 16, 16 and 32 bits: 64 lanes' limbs of 16 bits sum to less than 2^22, and
+            // the upper limb is wanted modulo 2^32
             const uint32_t s_pop = wave_prefix_sum((uint32_t)__builtin_popcountll(fr));
             const uint32_t s_a = wave_prefix_sum((uint32_t)term & 0xFFFFu);
             const uint32_t s_b = wave_prefix_sum(((uint32_t)term >> 16) & 0xFFFFu);
@@ -242,13 +222,12 @@ __global__ __launch_bounds__(kLanes* kWavesPerWG) void batch_objects_kernel(cons
 hipError_t launch_batch_objects(const ObjectsParams& p, bool clipped, hipStream_t stream) {
     // every index the kernel forms stays inside the plane (p.boards, the range's end, is inside the batch: the
     // caller's to get right), the counts and the records
-    if (!p.plane || !p.counts || !p.objects || p.first < 0 || p.boards <= p.first || p.boards > kMaxBoards ||
-        p.width < 1 || p.width > kLanes || p.height < 1 || p.height > kLanes ||
-        p.boards_per_wave != batch_lanes(p.height, p.boards).boards_per_wave || (p.reach != 1 && p.reach != 2) ||
+    if (!launch_geometry_ok(p.boards, p.width, p.height, p.boards_per_wave, clipped, p.vis_w, p.vis_h) || !p.plane ||
+        !p.counts || !p.objects || p.first < 0 || p.boards <= p.first || (p.reach != 1 && p.reach != 2) ||
         p.max_objects < 1 || p.max_objects > kMaxBoardObjects || (!clipped && (p.width < 3 || p.height < 3)))
         return hipErrorInvalidValue;
-    const int64_t waves = batch_lanes(p.height, (int64_t)p.boards - p.first).waves;
-    const dim3 grid((unsigned)((waves + kWavesPerWG - 1) / kWavesPerWG)), block(kLanes * kWavesPerWG);
+    // the waves of the range's boards, not of the batch's
+    const dim3 grid = launch_grid(p.height, (int64_t)p.boards - p.first), block(kLanes * kWavesPerWG);
     return clipped ? gol::launch_kernel(batch_objects_kernel<true>, grid, block, stream, p)
                    : gol::launch_kernel(batch_objects_kernel<false>, grid, block, stream, p);
 }
