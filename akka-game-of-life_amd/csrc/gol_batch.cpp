@@ -1,9 +1,9 @@
 // gol_batch.cpp -- C ABI of the batch engine (include/gol.h gol_batch_*,
-// gol_cycle_*, gol_find_batch*, gol_objects_batch*, gol_census_batch* and
-// gol_rules_batch_*; DESIGN.md sections 5f to 5k): many independent boards of at most 64 x 64
+// gol_cycle_*, gol_find_batch*, gol_objects_batch*, gol_census_batch*,
+// gol_rules_batch_* and gol_soup_batch*; DESIGN.md sections 5f to 5l): many independent boards of at most 64 x 64
 // stored cells stepped by one launch (kernels: gol_batch.hip), searched by one
-// (gol_batch_find.hip), cut into their objects by one (gol_batch_objects.hip)
-// and those tallied by one (gol_batch_census.hip).  A
+// (gol_batch_find.hip), cut into their objects by one (gol_batch_objects.hip),
+// those tallied by one (gol_batch_census.hip) and filled with soups by one (gol_batch_soup.hip).  A
 // handle type of its own: it shares the error conventions and the HIP status
 // discipline with the contexts (gol_ctx.h), and nothing else -- no planner, no
 // step kernel.  Every device buffer of the handle has one owner (DevBuf), the
@@ -121,6 +121,10 @@ struct gol_batch {
         std::vector<uint32_t> host;
         bool on = false;
     } rules;
+    // gol_soup_batch: the fundamental domain's row masks of the call's spec, allocated by the first call
+    struct {
+        DevBuf<unsigned long long> domain;  // [golsoup::kMaxSide]
+    } soup;
     std::string err;
 };
 
@@ -238,6 +242,15 @@ int rules_refusal(gol_batch* b, const char* fn, const char* why, const golbatch:
                          (long long)(first + which), rules[which], why);
     return batch_err(b, GOL_EINVAL, "%s: %s (first %lld, count %lld, batch of %d)", fn, why, (long long)first,
                      (long long)count, g.boards);
+}
+
+// batch_soup_args' refusal as a message, with the window and the range it is about
+int soup_refusal(gol_batch* b, const char* fn, const char* why, const golbatch::Geometry& g, const gol_soup_spec* s,
+                 int64_t first, int64_t count) {
+    if (!s) return batch_err(b, GOL_EINVAL, "%s: %s", fn, why);
+    return batch_err(b, GOL_EINVAL, "%s: %s (window %d x %d at (%d, %d), density %d, symmetry %d, first %lld, count "
+                     "%lld, batch of %d boards %d x %d)", fn, why, s->w, s->h, s->x, s->y, s->density, s->symmetry,
+                     (long long)first, (long long)count, g.boards, g.width, g.height);
 }
 
 // batch_census_args for a call of this handle: the request's handle fields filled in
@@ -856,6 +869,56 @@ int gol_rules_batch_get(gol_batch* batch, int64_t first, int64_t count, uint32_t
         std::fill(rules_out, rules_out + count, golbatch::rule_word(batch->birth, batch->survive));
     else
         std::copy(batch->rules.host.begin() + first, batch->rules.host.begin() + first + count, rules_out);
+    return GOL_OK;
+}
+
+int gol_soup_batch_check(const gol_batch_config* cfg, const gol_soup_spec* spec, int64_t first, int64_t count) {
+    if (!cfg) return batch_err(nullptr, GOL_EINVAL, "gol_soup_batch_check: null configuration");
+    golbatch::Geometry g;
+    if (const int rc = config_geometry(cfg, &g)) return rc;
+    if (const char* why = golbatch::batch_soup_args(g, spec, first, count))
+        return soup_refusal(nullptr, "gol_soup_batch_check", why, g, spec, first, count);
+    return GOL_OK;
+}
+
+int gol_soup_batch(gol_batch* batch, const gol_soup_spec* spec, int64_t first, int64_t count) {
+    if (!batch) return batch_err(nullptr, GOL_EINVAL, "gol_soup_batch: null handle");
+    if (const char* why = golbatch::batch_soup_args(batch->geo, spec, first, count))
+        return soup_refusal(batch, "gol_soup_batch", why, batch->geo, spec, first, count);
+    golsoup::Plan plan;  // the domain's row masks are the spec's alone: computed here, read by every wave
+    golsoup::make_plan(*spec, &plan);
+    BATCH_HIP(batch, hipSetDevice(batch->device));
+    if (!batch->soup.domain.grow(golsoup::kMaxSide, "gol_soup_batch: hipFree"))
+        return batch_err(batch, GOL_ENOMEM, "gol_soup_batch: hipMalloc of %zu bytes for the domain words failed; "
+                         "nothing changed", (size_t)golsoup::kMaxSide * sizeof(uint64_t));
+    // `plan` outlives the copy: the call synchronises before it returns
+    BATCH_HIP(batch, hipMemcpyAsync(batch->soup.domain.dev, plan.domain, sizeof plan.domain, hipMemcpyHostToDevice,
+                                    batch->stream));
+    auto p = launch_params<golbatch::SoupParams>(batch);
+    p.plane = batch->plane.dev;
+    p.domain = batch->soup.domain.dev;
+    p.spec = *spec;
+    p.first = (int32_t)first;  // inside the batch: both fit
+    p.count = (int32_t)count;
+    BATCH_HIP(batch, golbatch::launch_batch_soup(p, batch->stream));
+    BATCH_HIP(batch, hipStreamSynchronize(batch->stream));
+    batch->epoch = 0;
+    return GOL_OK;
+}
+
+int gol_soup_batch_rows(const gol_batch_config* cfg, const gol_soup_spec* spec, int64_t first, int64_t count,
+                        uint64_t* rows_out, size_t capacity) {
+    if (!cfg) return batch_err(nullptr, GOL_EINVAL, "gol_soup_batch_rows: null configuration");
+    golbatch::Geometry g;
+    if (const int rc = config_geometry(cfg, &g)) return rc;
+    if (const char* why = golbatch::batch_soup_args(g, spec, first, count))
+        return soup_refusal(nullptr, "gol_soup_batch_rows", why, g, spec, first, count);
+    if (!rows_out) return batch_err(nullptr, GOL_EINVAL, "gol_soup_batch_rows: rows_out is null");
+    const size_t need = (size_t)count * (size_t)g.height;  // <= 2^22 * 2^6
+    if (capacity < need)
+        return batch_err(nullptr, GOL_EINVAL, "gol_soup_batch_rows: rows_out holds %zu entries, %lld boards x %d rows "
+                         "need %zu", capacity, (long long)count, g.height, need);
+    golsoup::batch_rows(*spec, g.height, first, count, rows_out);
     return GOL_OK;
 }
 

@@ -1,6 +1,6 @@
 // gol_batch.h -- internal interface between the batch engine's C-ABI unit
 // (gol_batch.cpp) and its gfx950 kernels (gol_batch*.hip); DESIGN.md sections
-// 5f to 5k: the lane mapping, the pure validators, the launch parameters and
+// 5f to 5l: the lane mapping, the pure validators, the launch parameters and
 // what every launcher checks of them.  A header of its own: the step kernels'
 // units include none of it.  Not installed.
 #pragma once
@@ -8,6 +8,7 @@
 #include <stdint.h>
 
 #include "../../include/gol.h"
+#include "gol_soup.h"
 
 namespace golbatch {
 
@@ -338,5 +339,25 @@ struct CensusTallyParams {
 hipError_t launch_census_clear(const CensusTable& t, hipStream_t stream);
 hipError_t launch_census_tally(const CensusTallyParams& p, hipStream_t stream);
 hipError_t launch_census_compact(const CensusTable& t, uint4* out, uint64_t out_capacity, hipStream_t stream);
+
+// Soups (gol_soup_batch*).  The validator, the raw bits
+// and the groups are gol_soup.h's, which needs no HIP.
+inline const char* batch_soup_args(const Geometry& g, const gol_soup_spec* s, int64_t first, int64_t count) {
+    return golsoup::soup_args(g.width, g.height, g.boards, s, first, count);
+}
+
+// One launch: boards first .. first + count - 1 become the soups of `spec`.
+struct SoupParams {
+    unsigned long long* plane;         // boards * height rows
+    const unsigned long long* domain;  // [golsoup::kMaxSide]: the fundamental domain's row masks (golsoup::make_plan)
+    gol_soup_spec spec;
+    int32_t boards, width, height, boards_per_wave;
+    int32_t first, count;
+    uint32_t steps;  // golsoup::steps(spec.symmetry): the launcher's to fill in
+};
+
+// gol_batch_soup.hip.  hipErrorInvalidValue for parameters outside what the
+// kernel indexes safely: everything batch_soup_args refuses among them.
+hipError_t launch_batch_soup(const SoupParams& p, hipStream_t stream);
 
 }  // namespace golbatch

@@ -189,6 +189,24 @@ GOL_FIND_BATCH_AUTO_CUT = 2048
 # gol_rules_batch_*: the bits a rule word may have set -- GOL_BATCH_RULE(birth, survive) (include/gol.h)
 GOL_BATCH_RULE_BITS = 0x01FF01FF
 
+# gol_soup_batch*: the symmetries (include/gol.h GOL_SOUP_*), by name
+SOUP_SYMMETRIES = {"C1": 0, "C2": 1, "C4": 2, "D2_X": 3, "D2_Y": 4, "D2_DIAG": 5, "D4_PLUS": 6, "D4_DIAG": 7, "D8": 8}
+
+
+class GolSoupSpec(ctypes.Structure):
+    """gol_soup_spec: the soups of a batch (gol_soup_batch*), 40 bytes."""
+    _fields_ = [
+        ("seed", ctypes.c_uint64),
+        ("index0", ctypes.c_uint64),
+        ("x", ctypes.c_int32),
+        ("y", ctypes.c_int32),
+        ("w", ctypes.c_int32),
+        ("h", ctypes.c_int32),
+        ("density", ctypes.c_int32),
+        ("symmetry", ctypes.c_int32),
+    ]
+
+
 # gol_write_region modes (include/gol.h GOL_REGION_*)
 GOL_REGION_COPY = 0
 GOL_REGION_OR = 1
@@ -301,6 +319,11 @@ _SIGNATURES = {
     "gol_rules_batch_check": (_c.c_int, [ctypes.POINTER(GolBatchConfig), _c.c_int64, _c.c_int64, _u32p]),
     "gol_rules_batch_set": (_c.c_int, [_vp, _c.c_int64, _c.c_int64, _u32p]),
     "gol_rules_batch_get": (_c.c_int, [_vp, _c.c_int64, _c.c_int64, _u32p]),
+    "gol_soup_batch_check": (_c.c_int, [ctypes.POINTER(GolBatchConfig), ctypes.POINTER(GolSoupSpec), _c.c_int64,
+                                        _c.c_int64]),
+    "gol_soup_batch": (_c.c_int, [_vp, ctypes.POINTER(GolSoupSpec), _c.c_int64, _c.c_int64]),
+    "gol_soup_batch_rows": (_c.c_int, [ctypes.POINTER(GolBatchConfig), ctypes.POINTER(GolSoupSpec), _c.c_int64,
+                                       _c.c_int64, _u64p, _c.c_size_t]),
 }
 
 

@@ -6,6 +6,9 @@ geometry, each at most 64 x 64 stored cells, under one rule or a rule per
 board (set_rules: a rule sweep), and advances all of them per launch through libgol's gol_batch_* entry points: random soups until
 they settle, one pattern under many perturbations, or many copies of the
 reference's own 7 x 7 board.  A board's row is one uint64 (bit x = cell x).
+GolBatch.soup generates the soups on the device (a window of any density,
+nine symmetries, soup number n a function of the seed and n alone), and
+soup_rows gives any one of them back on the host.
 """
 from __future__ import annotations
 
@@ -23,6 +26,8 @@ OBJECT_DTYPE = P.OBJECT_DTYPE
 CENSUS_DTYPE = np.dtype([("hash", "<u8"), ("w", "u1"), ("h", "u1"), ("population", "<u2"), ("first_call", "<u4"),
                          ("count", "<u8"), ("first_board", "<u4"), ("first_x", "u1"), ("first_y", "u1"),
                          ("reserved", "<u2")])
+# the symmetries GolBatch.soup and soup_rows take (include/gol.h GOL_SOUP_*), in their order
+SOUP_SYMMETRIES = tuple(N.SOUP_SYMMETRIES)
 
 
 class GolBatch:
@@ -75,6 +80,21 @@ class GolBatch:
     # -- state -------------------------------------------------------------
     def seed(self, seed: int = 0x5EED) -> None:
         self._chk(N.lib.gol_batch_seed(self._h, seed))
+
+    def soup(self, seed: int, *, window: tuple[int, int, int, int] | None = None, density: float | int = 0.5,
+             symmetry: str = "C1", index0: int = 0, first: int = 0, count: int | None = None) -> None:
+        """Boards first .. first + count - 1 become random soups, generated
+        on the device (gol_soup_batch): board b holds soup number index0 + b,
+        a pure function of (seed, that number) which soup_rows reproduces
+        anywhere.  `window` is (x, y, w, h) in stored cells, the rest of the
+        board dead (None: the whole stored board); `density` the probability
+        of a live cell, a float rounded to n / 256 or an int taken as n, n in
+        1 .. 255; `symmetry` one of SOUP_SYMMETRIES (C4, D2_DIAG, D4_DIAG and
+        D8 need a square window).  The other boards keep their cells; the
+        epoch goes to 0 as after load, per-board rules stay."""
+        spec = _soup_spec(self.width, self.height, seed, index0, window, density, symmetry)
+        count = self.boards - first if count is None else count
+        self._chk(N.lib.gol_soup_batch(self._h, ctypes.byref(spec), first, count))
 
     def load(self, x, first: int = 0) -> None:
         """Boards first .. first + n - 1 from uint64 [n][H] rows or uint8
@@ -324,6 +344,37 @@ class GolBatch:
     def set_chunk(self, n: int) -> None:
         """Generations per launch (0: automatic); results never depend on it."""
         self._chk(N.lib.gol_batch_set_chunk(self._h, n))
+
+
+def _soup_spec(width, height, seed, index0, window, density, symmetry) -> N.GolSoupSpec:
+    if symmetry not in N.SOUP_SYMMETRIES:
+        raise ValueError(f"symmetry must be one of {', '.join(SOUP_SYMMETRIES)}, not {symmetry!r}")
+    spec = N.GolSoupSpec()
+    spec.seed, spec.index0 = seed & 0xFFFFFFFFFFFFFFFF, index0 & 0xFFFFFFFFFFFFFFFF
+    spec.x, spec.y, spec.w, spec.h = (0, 0, width, height) if window is None else window
+    spec.density = density if isinstance(density, (int, np.integer)) else int(round(float(density) * 256))
+    spec.symmetry = N.SOUP_SYMMETRIES[symmetry]
+    return spec
+
+
+def soup_rows(width: int, height: int, seed: int, index, *, window=None, density=0.5, symmetry: str = "C1",
+              topology: str = "torus", vis: tuple[int, int] | None = None) -> np.ndarray:
+    """uint64 [n][H]: the boards GolBatch.soup gives soups number `index` (one
+    number or n of them) on boards of this geometry, computed on the host
+    (gol_soup_batch_rows: no device, no handle).  The reproducer: the soup
+    behind a census entry is number index0 + first_board of the soup call
+    that preceded census call first_call."""
+    cfg = N.GolBatchConfig()
+    cfg.boards, cfg.width, cfg.height = 1, width, height
+    cfg.topology = {"torus": N.GOL_TORUS, "ref-clipped": N.GOL_REF_CLIPPED}[topology]
+    cfg.vis_width, cfg.vis_height = vis if vis is not None else (0, 0)
+    numbers = [int(i) for i in np.atleast_1d(np.asarray(index, dtype=object)).reshape(-1)]
+    out = np.zeros((len(numbers), height), dtype=np.uint64)
+    for i, n in enumerate(numbers):
+        spec = _soup_spec(width, height, seed, n, window, density, symmetry)
+        N.check_batch(N.lib.gol_soup_batch_rows(ctypes.byref(cfg), ctypes.byref(spec), 0, 1,
+                                                out[i].ctypes.data_as(N._u64p), height))
+    return out
 
 
 def rule_sweep_words(births, survives) -> np.ndarray:

@@ -67,7 +67,8 @@ extern "C" {
  * gol_objects_batch_stats) and its census (gol_census_batch_check,
  * gol_census_batch_begin, gol_census_batch_add, gol_census_batch_add_records,
  * gol_census_batch_read, gol_census_batch_stats) and its per-board rules
- * (gol_rules_batch_check, gol_rules_batch_set, gol_rules_batch_get). */
+ * (gol_rules_batch_check, gol_rules_batch_set, gol_rules_batch_get) and its
+ * soups (gol_soup_batch_check, gol_soup_batch, gol_soup_batch_rows). */
 #define GOL_ABI_VERSION 2
 
 /* Return codes. */
@@ -895,6 +896,76 @@ int gol_census_batch_stats(gol_batch* batch, uint64_t* calls, uint64_t* seen, ui
 int gol_rules_batch_check(const gol_batch_config* cfg, int64_t first, int64_t count, const uint32_t* rules);
 int gol_rules_batch_set(gol_batch* batch, int64_t first, int64_t count, const uint32_t* rules);
 int gol_rules_batch_get(gol_batch* batch, int64_t first, int64_t count, uint32_t* rules_out);
+
+/* Soups: the boards a soup search starts from,
+ * generated on the device -- a random window of any density in an otherwise
+ * dead board, under one of nine symmetries, soup number n a pure function of
+ * (seed, n) so that a census entry's first_call and first_board lead back to
+ * the soup that produced it.  gol_batch_seed keeps its own definition (every
+ * stored cell a fair coin).  The names are gol_soup_batch*: the handle is the
+ * batch, the capability its own.
+ *
+ * Raw bits.  mix(seed, c) is gol_batch_seed's function of a counter:
+ * z = seed + 0x9E3779B97F4A7C15 (c + 1), z = (z ^ (z >> 30))
+ * 0xBF58476D1CE4E5B9, z = (z ^ (z >> 27)) 0x94D049BB133111EB, z ^= z >> 31
+ * (mod 2^64).  For soup number s, window row v and bit plane j in 0..7,
+ * Z[j] = mix(seed, (s * 64 + v) * 8 + j) (mod 2^64); window column u has the
+ * 8-bit value t(u) = sum over j of (bit u of Z[j]) << j, and raw(u, v) is
+ * t(u) < density: a cell lives with probability density / 256.
+ *
+ * Symmetry.  On window coordinates X is (u, v) -> (w - 1 - u, v), Y is
+ * (u, v) -> (u, h - 1 - v), T is (u, v) -> (v, u) and R is (u, v) ->
+ * (h - 1 - v, u); T and R need w == h.  The groups: C1 {e}; C2 {e, XY};
+ * C4 {e, R, R^2, R^3}; D2_X {e, X}; D2_Y {e, Y}; D2_DIAG {e, T};
+ * D4_PLUS {e, X, Y, XY}; D4_DIAG {e, T, XY, T XY}; D8 all eight.  Window cell
+ * (u, v) is raw(u*, v*), (u*, v*) the member of the orbit of (u, v) under the
+ * group with the smallest (v', u') in lexicographic order.  The parity of w
+ * and h decides whether an axis runs through cells or between them.  Stored
+ * cell (x + u, y + v) of the board takes that value and every other stored
+ * cell is dead, on both topologies: on a clipped board the stored cells
+ * outside the visible extent are cells like any other.
+ *
+ * gol_soup_batch: boards first .. first + count - 1 become soups index0 + b,
+ * b the board's number in the batch (mod 2^64), so giving a part of a batch
+ * its soups again reproduces the boards it had; the other boards keep their
+ * cells.  It resets the epoch to 0 as gol_batch_load does, and keeps the
+ * per-board rules.  One launch; synchronises.
+ *
+ * gol_soup_batch_rows writes the same boards to host memory in the host
+ * layout ([count][height]; capacity in entries) and needs neither a device
+ * nor a handle: a census exemplar's soup comes back from
+ * (seed, index0 + first_board) in any process.
+ *
+ * Refused with GOL_EINVAL and a message, before any device work and with
+ * nothing written: a NULL argument, w < 1 or h < 1, a window not inside the
+ * stored board (x, y >= 0, x + w <= width, y + h <= height; no wrap), density
+ * outside 1 .. 255, an unknown symmetry, w != h with C4, D2_DIAG, D4_DIAG or
+ * D8, boards [first, first + count) outside the batch, and for
+ * gol_soup_batch_rows a capacity below count * height.  gol_soup_batch_check
+ * validates the same arguments for a geometry and needs no device.  The
+ * device's 64 domain words belong to the handle (GOL_ENOMEM, and nothing
+ * changed, if they cannot be had) and are not part of
+ * gol_batch_geometry_get's device_bytes. */
+#define GOL_SOUP_C1 0
+#define GOL_SOUP_C2 1
+#define GOL_SOUP_C4 2
+#define GOL_SOUP_D2_X 3
+#define GOL_SOUP_D2_Y 4
+#define GOL_SOUP_D2_DIAG 5
+#define GOL_SOUP_D4_PLUS 6
+#define GOL_SOUP_D4_DIAG 7
+#define GOL_SOUP_D8 8
+typedef struct gol_soup_spec {
+    uint64_t seed;
+    uint64_t index0;     /* board b holds soup number index0 + b (mod 2^64) */
+    int32_t  x, y, w, h; /* the window, in stored cells; the rest of the board is dead */
+    int32_t  density;    /* 1 .. 255: a cell lives with probability density / 256 */
+    int32_t  symmetry;   /* GOL_SOUP_C1 .. GOL_SOUP_D8 */
+} gol_soup_spec;         /* 40 bytes */
+int gol_soup_batch_check(const gol_batch_config* cfg, const gol_soup_spec* spec, int64_t first, int64_t count);
+int gol_soup_batch(gol_batch* batch, const gol_soup_spec* spec, int64_t first, int64_t count);
+int gol_soup_batch_rows(const gol_batch_config* cfg, const gol_soup_spec* spec, int64_t first, int64_t count,
+                        uint64_t* rows_out, size_t capacity);
 
 /* Kernel timing: when enabled, the dominant step-kernel launch of every pass
  * (the whole shard, or a sharded shard's interior rows) is bracketed by HIP
