@@ -7,6 +7,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <algorithm>
+
 #include "../../include/gol.h"
 #include "gol_soup.h"
 
@@ -62,7 +64,9 @@ inline const char* batch_geometry(const gol_batch_config& c, Geometry* g) {
         // on a board where some cell has no visible neighbour
         vw = c.vis_width > 0 ? c.vis_width : c.width - 1;
         vh = c.vis_height > 0 ? c.vis_height : c.height - 1;
-        if (vw < 1 || vh < 1 || (vw == 1 && vh == 1) || c.width > vw + 1 || c.height > vh + 1)
+        // (extents beyond the stored board show no more than the board: a single visible cell stays one)
+        if (vw < 1 || vh < 1 || (std::min(vw, c.width) == 1 && std::min(vh, c.height) == 1) || c.width > vw + 1 ||
+            c.height > vh + 1)
             return "ref-clipped board on which a cell has no visible neighbour: the reference never completes a "
                    "generation on such a board (NextStateCellGathererActor.scala:26-27,39-58, "
                    "CellActor.scala:75-76,92-94)";

@@ -248,7 +248,9 @@ int gol_create(gol_ctx** out, const gol_config* cfg) {
         // advanced with results the reference never produces.
         const int64_t vw = c.vis_width > 0 ? c.vis_width : c.width - 1;
         const int64_t vh = c.vis_height > 0 ? c.vis_height : c.height - 1;
-        if (vw < 1 || vh < 1 || (vw == 1 && vh == 1) || c.width > vw + 1 || c.height > vh + 1)
+        // (extents beyond the stored board show no more than the board: a single visible cell stays one)
+        if (vw < 1 || vh < 1 || (std::min(vw, c.width) == 1 && std::min(vh, c.height) == 1) || c.width > vw + 1 ||
+            c.height > vh + 1)
             return set_err(nullptr, GOL_EINVAL,
                            "ref-clipped board %lld x %lld with visible extents %lld x %lld: a cell has no visible "
                            "neighbour, and the reference never completes a generation on such a board "

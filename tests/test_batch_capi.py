@@ -127,6 +127,10 @@ def test_geometry_accepts_the_shapes_the_gpu_tests_use():
     dict(boards=-1), dict(boards=(1 << 22) + 1), dict(topology=2), dict(topology=-1), dict(rule=(0x200, 0x00C)),
     dict(width=10, height=10, topology=N.GOL_REF_CLIPPED, vis=(7, 9)),
     dict(width=10, height=10, topology=N.GOL_REF_CLIPPED, vis=(9, 7)),
+    # found by tests/test_sweep_cases.py: visible extents beyond the stored board still leave one visible cell
+    dict(width=1, height=1, topology=N.GOL_REF_CLIPPED, vis=(2, 2)),
+    dict(width=2, height=1, topology=N.GOL_REF_CLIPPED, vis=(1, 2)),
+    dict(width=1, height=2, topology=N.GOL_REF_CLIPPED, vis=(2, 1)),
 ])
 def test_geometry_refusals(kw):
     rc, _ = _geometry(_cfg(**kw))

@@ -66,6 +66,12 @@ def test_visible_extents_that_strand_cells_are_refused():
     assert _create(10, 10, vis=(7, 9)) == N.GOL_EINVAL
     assert _create(10, 10, vis=(9, 7)) == N.GOL_EINVAL
     assert _create(10, 10, vis=(9, 9)) in (N.GOL_OK, N.GOL_ENODEV)
+    # found by tests/test_sweep_cases.py: extents beyond the stored board show no more than the board, so these
+    # boards have one visible cell, which has nobody to ask -- as (1, 1) on them, refused before
+    assert _create(1, 1, vis=(2, 2)) == N.GOL_EINVAL
+    assert _create(2, 1, vis=(1, 2)) == N.GOL_EINVAL
+    assert _create(1, 2, vis=(2, 1)) == N.GOL_EINVAL
+    assert _create(1, 2, vis=(2, 2)) in (N.GOL_OK, N.GOL_ENODEV)
 
 
 def test_torus_tiny_boards_still_accepted():
